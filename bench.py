@@ -7,11 +7,16 @@ generated on the device and are resident in HBM before the timed region.  A "ste
 pass of the extension kernel over the whole batch (for N>1: over every rank's shard, plus the
 gather of the result records to rank 0 over RCCL/xGMI, overlapped with the next step).
 
-Also measured in the same run (not part of `value`): the FM-index rank() point-query kernel
-on a 3 Gbp-sized index (the second half of BASELINE.json's metric), reported as `rank_roofline`,
-and the CPU oracle timed on the host cores (`cpu_baseline`).
+A plain run sets up, warms up, times the steps and prints the result line (the last stdout line);
+`--dump-outputs DIR` also writes what the last timed step computed (benchlib/dump.py).  With
+`--full` the same run also checks a sample against the CPU oracle (`parity`), times the all-int32
+kernel (`roofline.a32`) and runs the other legs (not part of `value`): the FM-index rank()
+point-query kernel on a 3 Gbp-sized index (the second half of BASELINE.json's metric), reported as
+`rank_roofline`, the seed / end-to-end / full-matrix / drop-in stream legs, and the CPU oracle timed
+on the host cores (`cpu_baseline`); every leg also goes to the legs file.
 
   python bench.py --gpus 1 --steps 20 --warmup 3
+  python bench.py --gpus 1 --steps 20 --warmup 3 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -128,6 +133,8 @@ def parse():
     ap.add_argument("--legs-file", default=None, help="where the full per-leg objects go (default: gpurun_out/bench_legs.json if that directory exists, else ./bench_legs.json)")
     ap.add_argument("--ref-app-reads", type=int, default=5_000_000)
     ap.add_argument("--cpu-sample", type=int, default=10_000_000)
+    ap.add_argument("--full", action="store_true", help="also run the oracle parity gate, the all-int32 timing and every other leg (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's scores and sinks to DIR/*.npy (float64)")
     return ap.parse_args()
 
 
@@ -136,6 +143,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.steps is None:
         a.steps = 200
+    if a.only is not None:
+        a.full = True       # --only runs one leg of the full run, as the full run runs it
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("NVBIO_BENCH_SHARE_GPU") == "1":
@@ -275,9 +284,9 @@ def main():
                 pending[b] = torch.cuda.Event()
                 pending[b].record(comm_stream)
 
-    # ---------------------------------------------------------------- parity gate (sample vs oracle)
+    # ---------------------------------------------------------------- parity gate (sample vs oracle; --full)
     parity = None
-    if rank == 0:
+    if rank == 0 and a.full:
         from oracle import pyoracle as O          # checker only
         import numpy as np
         launch(outs[0])
@@ -313,9 +322,12 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     kern_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / max(a.steps, 1)
-    # the same launch on the all-int32 kernel (what runs when the host cannot prove the 16-bit form exact)
+    if rank == 0 and a.dump_outputs and a.steps > 0:
+        from benchlib import dump
+        dump.write_outputs(a.dump_outputs, *outs[(a.steps - 1) & 1])
+    # the same launch on the all-int32 kernel (what runs when the host cannot prove the 16-bit form exact; --full)
     a32_ms = None
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and a.full:
         nvb.set_test_switch("NVBIO_HIP_FORCE_32BIT", "1")
         launch(outs[1]); torch.cuda.synchronize()
         ev32 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
@@ -373,32 +385,36 @@ def main():
             "roofline": roofline, "parity": parity,
         }
 
-    # ---------------------------------------------------------------- FM-index rank leg (rank 0, N == 1 only)
-    if rank == 0 and world == 1 and not (a.no_rank and a.no_seed and a.no_e2e):
+    # ---------------------------------------------------------------- FM-index rank leg and the other legs (rank 0, N == 1 only; --full)
+    if rank == 0 and world == 1 and a.full and not (a.no_rank and a.no_seed and a.no_e2e):
         del patterns, texts, outs
         torch.cuda.empty_cache()
         out.update(fm_legs(a, dev))
-    if rank == 0 and world == 1 and not a.no_full:
+    if rank == 0 and world == 1 and a.full and not a.no_full:
         out["full_dp_leg"] = full_dp_leg(a, dev)
         out["compat_stream_leg"] = compat_stream_leg(a, dev)
-    if rank == 0 and world == 1 and not a.no_e2e and not a.no_repeat_rich:
+    if rank == 0 and world == 1 and a.full and not a.no_e2e and not a.no_repeat_rich:
         torch.cuda.empty_cache()
         nvb.lib().nvbio_hip_device_trim()
         out.setdefault("e2e_leg", {})["repeat_rich"] = repeat_rich_leg(a, dev)
-    if rank == 0 and world == 1 and a.ref_app:
+    if rank == 0 and world == 1 and a.full and a.ref_app:
         torch.cuda.empty_cache()
         out["ref_nvbowtie_leg"] = ref_nvbowtie_leg(a, dev)
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and a.full and not a.no_cpu:
         out["cpu_baseline"] = cpu_leg(a, *W.make_sw_batch(min(n, a.cpu_sample), READ_LEN, REF_LEN, seed=0x5EED0002, device=dev))
     # ---------------------------------------------------------------- nvBowtie end to end, sharded (N > 1): BASELINE config 4's "1 vs 8 GPU shard"
-    if world > 1 and not a.no_e2e:
+    if world > 1 and a.full and not a.no_e2e:
         del patterns, texts, outs
         torch.cuda.empty_cache()
         leg = e2e_sharded_leg(a, dev, rank, world, barrier, cxx_comm)
         if rank == 0:
             out["e2e_sharded_leg"] = leg
     if rank == 0:
-        emit(out, a.legs_file)
+        if a.full:
+            emit(out, a.legs_file)
+        else:
+            from benchlib import headline as H
+            print(H.headline_line(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
 

@@ -31,7 +31,7 @@ def test_two_ranks_share_one_gpu_through_the_whole_bench(route):
         env["NVBIO_BENCH_HOST_TRANSPORT"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--reads", "300000",
-           "--genome", "4e6", "--e2e-reads", "40000"]
+           "--genome", "4e6", "--e2e-reads", "40000", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

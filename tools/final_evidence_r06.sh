@@ -6,10 +6,10 @@ R=$PWD
 O=$R/gpurun_out/r06
 mkdir -p $O
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1
-( time python bench.py --steps 20 --warmup 5 > $O/bench_n1.json.log 2> $O/bench_n1.err ) 2> $O/bench_n1.time
+( time python bench.py --full --steps 20 --warmup 5 > $O/bench_n1.json.log 2> $O/bench_n1.err ) 2> $O/bench_n1.time
 cp $R/gpurun_out/bench_legs.json $O/bench_legs.json 2>/dev/null
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pb -o b -- python $R/bench.py --steps 20 --warmup 5 --no-repeat-rich > $O/bench_prof.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $TMPDIR/pb -o b -- python $R/bench.py --full --steps 20 --warmup 5 --no-repeat-rich > $O/bench_prof.log 2>&1
 find /tmp/pb -name "*kernel_stats.csv" -exec cp {} $O/bench_kernel_stats.csv \;
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/po -o own -- python $R/tools/own_driver_3gbp.py --workers 1 --no-stage-clock --reps 1 > $O/own_prof.log 2>&1
 find /tmp/po -name "*kernel_stats.csv" -exec cp {} $O/own_driver_3gbp_repeats_kernel_stats_full.csv \;
