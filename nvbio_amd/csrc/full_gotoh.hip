@@ -1068,12 +1068,16 @@ static int full_score_core(
     // the 16-bit sweep's sentinel and range reasoning assume that no gap move earns score, on either string
     const bool gaps_cost = scheme->gap_open <= 0 && scheme->gap_ext <= 0 && (!qual || (qual->text_gap_open <= 0 && qual->text_gap_ext <= 0));
     bool trunc = !(gaps_cost && span * A < 30000);
+    // the largest score one aligned pair can add -- a mismatch or a quality-LUT entry may lie above match (on the quality entry
+    // scheme->mismatch is the LUT's most negative entry): LOCAL's H and GLOBAL's interior H are bounded by M times it, not by M * match
+    int32_t best_pair = std::max(scheme->match, scheme->mismatch);
+    if (qual) for (int i = 0; i < 256; ++i) best_pair = std::max(best_pair, qual->mismatch[i]);
     if (trunc && gaps_cost && type == NVBIO_HIP_GLOBAL)
     {
         // GLOBAL, tighter: (M + N) * max|cost| overestimates badly when the expensive costs are not the gap extensions.  What the sweep
         // holds: the two boundary lines themselves, H(r,-1) = col_go + col_ge*r and H(-1,c) = row_go + row_ge*c; interior H, each at
         // least the value of reaching it by one gap run from either boundary line (H is a maximum over paths, those paths included) and
-        // at most M times the best pair score; E, F, H + G_o and the diagonal sum within one gap open + one extension + one substitution
+        // at most M times the best pair score (the LUT's entries included); E, F, H + G_o and the diagonal sum within one gap open + one extension + one substitution
         // of an H.  All inside int16 => the 16-bit sweep and the reference's int16 boundary column are both exact.
         const int64_t row_line = iabs(p.row_go) + iabs(p.row_ge) * int64_t(maxN), col_line = iabs(p.col_go) + iabs(p.col_ge) * int64_t(maxM);
         const int64_t via_top  = row_line + iabs(scheme->gap_open) + iabs(scheme->gap_ext) * int64_t(maxM);
@@ -1081,7 +1085,7 @@ static int full_score_core(
         int64_t worst_sub = std::max(iabs(scheme->match), iabs(scheme->mismatch));
         if (qual) for (int i = 0; i < 256; ++i) worst_sub = std::max(worst_sub, iabs(qual->mismatch[i]));
         const int64_t low  = std::max(std::max(row_line, col_line), std::min(via_top, via_left)) + iabs(scheme->gap_open) + iabs(scheme->gap_ext) + worst_sub + 8;
-        const int64_t high = int64_t(maxM) * std::max<int64_t>(0, std::max(scheme->match, scheme->mismatch)) + worst_sub + 8;
+        const int64_t high = int64_t(maxM) * std::max<int64_t>(0, best_pair) + worst_sub + 8;
         if (low < 32000 && high < 32000) trunc = false;
     }
     if (striped)
@@ -1099,9 +1103,6 @@ static int full_score_core(
         g_last_kernel = "full_gotoh_striped_kernel";
         return launch_striped(sp, type, maxM, to_stream(stream));
     }
-    // the largest score one aligned pair can add: LOCAL's H is bounded by M times it, not by M * match
-    int32_t best_pair = std::max(scheme->match, scheme->mismatch);
-    if (qual) for (int i = 0; i < 256; ++i) best_pair = std::max(best_pair, qual->mismatch[i]);
     hipStream_t s = to_stream(stream);
     g_last_kernel = "full_gotoh_score_kernel";
     const int R = maxM <= 64u ? 1 : maxM <= 128u ? 2 : maxM <= 192u ? 3 : maxM <= 256u ? 4 : maxM <= 512u ? 8 : 16;
