@@ -76,6 +76,9 @@ struct A32 {
     static constexpr bool TABLE = false;
     static __device__ __forceinline__ uint32_t enc(uint32_t g)      { return g; }
     static __device__ __forceinline__ uint32_t enc_none()           { return 255u; }
+    static constexpr uint32_t ENC_BASE = 0u;
+    static __device__ __forceinline__ uint32_t enc_row(uint32_t g, uint32_t) { return g; }
+    static __device__ __forceinline__ void pin(T&)                  {}       // (the compiler places the 32-bit path's constants itself)
     static __device__ __forceinline__ T subst(uint32_t, uint32_t, uint32_t) { return 0; }
 
     // one interior band cell (gotoh_banded_inl.h:520-577): F, H, E and (LOCAL) the row's sink key
@@ -133,6 +136,14 @@ struct A16 {
     static constexpr bool TABLE = true;
     static __device__ __forceinline__ uint32_t enc(uint32_t g)      { uint32_t r; asm("v_mul_lo_u16 %0, %1, %2" : "=v"(r) : "v"(g), "v"(0x0202u)); return r | 0x0C0C0100u; }
     static __device__ __forceinline__ uint32_t enc_none()           { return 0x0C0C0C0Cu; }
+    // enc() of a row's entering text symbol in one instruction: the selector's fixed bytes come as a resident register (DPConsts::encb;
+    // 0x0202 * g has no bit in common with them, so the sum is the `or`)
+    static constexpr uint32_t ENC_BASE = 0x0C0C0100u;
+    static __device__ __forceinline__ uint32_t enc_row(uint32_t g, uint32_t base)
+    { uint32_t r; asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(g), "s"(0x0202u), "v"(base)); return r; }
+    // A constant the cell blocks take as a "v" operand lives in a VGPR for the whole job: an asm of no instructions whose result the
+    // compiler cannot know, so it cannot re-make the value from its SGPR with a v_mov_b32 in every row (it did: each row is a basic block)
+    static __device__ __forceinline__ void pin(T& v)                { asm("" : "+v"(v)); }
     static __device__ __forceinline__ T subst(uint32_t tlo, uint32_t thi, uint32_t sel) { return __builtin_amdgcn_perm(thi, tlo, sel); }
 
     // The same cell as one hand-scheduled instruction block: 2-cycle 16-bit VOP2 ops only (plus the
@@ -318,6 +329,15 @@ struct DPConsts {
     typename A::T GoE, Zstep;                // A::ROWTREND: G_o - G_e, |G_e|
     bool bytes;                              // the patterns are 8-bit strings
     uint32_t sMM, sXX;                       // table arithmetic: sM / sX in both halves of a dword
+    uint32_t encb = A::ENC_BASE;             // A::enc_row's fixed selector bytes
+    // keep what the rows' instruction blocks read as vector operands resident (A::pin)
+    __device__ __forceinline__ void pin()
+    {
+        A::pin(Ge); A::pin(inf); A::pin(sM); A::pin(sX);
+        if (A::ROWTREND) { A::pin(GoE); A::pin(Zstep); } else A::pin(Go);
+        if (A::ASYM) { A::pin(GeF); A::pin(dF); }
+        if (A::TABLE) { typename A::T e = encb; A::pin(e); encb = uint32_t(e); }
+    }
 };
 
 // after a block of 16 rows: a ring of 32 has turned half way round -- its halves change places, so that the next block's row R again finds
@@ -441,7 +461,8 @@ __device__ __forceinline__ void dp_row(DPState<BAND, A>& st, const DPConsts<A>& 
 }
 
 // FAST (table arithmetic only): the caller has checked that no row of this block lets a symbol past the text's end into the band
-template <int BAND, int TYPE, typename A, bool QUAL, bool FAST, int R, int END>
+// TAB: masks[q] is the finished table {tlo, thi} of pattern symbol q (no qualities: the table is one of sixteen per launch, built by the kernel's prologue)
+template <int BAND, int TYPE, typename A, bool QUAL, bool FAST, int R, int END, bool TAB = false>
 struct RowUnrollN {
     __device__ __forceinline__ static void run(DPState<BAND, A>& st, const DPConsts<A>& k,
         const uint32_t i0, const uint32_t M, const uint32_t N, const uint64_t P, const uint32_t T,
@@ -449,13 +470,14 @@ struct RowUnrollN {
     {
         typedef BandTraits<BAND> BT;
         const uint32_t i = i0 + R;
+        static_assert(!TAB || (FAST && !QUAL), "a ready-made table needs a mismatch score that is the same in every row");
         if (i < M)
         {
             const uint32_t qr = uint32_t(P >> (4 * R)) & 15u;
             const uint32_t gr = (T >> (2 * R)) & 3u;
             const bool past = !FAST && (i + BAND - 1 >= N);
             // the entering symbol as this row compares it, and as later rows read it back from the reference's text cache
-            const uint32_t g       = past ? A::enc_none() : A::enc(gr);
+            const uint32_t g       = past ? A::enc_none() : A::enc_row(gr, k.encb);
             const uint32_t g_store = past ? (BT::QUIRK ? A::enc(3u) : A::enc_none()) : g;        // the 2-bit cache keeps 255 & 3
             typename A::T sX = k.sX;
             if (QUAL) {
@@ -463,7 +485,8 @@ struct RowUnrollN {
                 sX = lut[(w >> (8 * (R & 3))) & 255u];          // mismatch(quality of row i), LDS
             }
             uint32_t tlo = 0, thi = 0;
-            if (FAST) {
+            if (TAB) { const uint2 t = masks[qr]; tlo = t.x; thi = t.y; }
+            else if (FAST) {
                 // entry v of the row's table: sM where v is the row's symbol, sX elsewhere (masks[q]: which 16-bit halves take sM)
                 const uint2 m = masks[qr];
                 const uint32_t xx = QUAL ? (uint32_t(sX) | (uint32_t(sX) << 16)) : k.sXX;
@@ -473,10 +496,10 @@ struct RowUnrollN {
             // (an 8-bit pattern's byte 255 arrives as code 15, fetch16_8bit: it equals a text position past the end, and nothing else)
             dp_row<BAND, TYPE, A, FAST, R>(st, k, sX, i, FAST ? 0u : ((k.bytes && qr == 15u) ? A::enc_none() : A::enc(qr)), g, g_store, tlo, thi);
         }
-        RowUnrollN<BAND, TYPE, A, QUAL, FAST, R + 1, END>::run(st, k, i0, M, N, P, T, Q, lut, masks);
+        RowUnrollN<BAND, TYPE, A, QUAL, FAST, R + 1, END, TAB>::run(st, k, i0, M, N, P, T, Q, lut, masks);
     }
 };
-template <int BAND, int TYPE, typename A, bool QUAL, bool FAST, int END> struct RowUnrollN<BAND, TYPE, A, QUAL, FAST, END, END> {
+template <int BAND, int TYPE, typename A, bool QUAL, bool FAST, int END, bool TAB> struct RowUnrollN<BAND, TYPE, A, QUAL, FAST, END, END, TAB> {
     __device__ __forceinline__ static void run(DPState<BAND, A>&, const DPConsts<A>&, uint32_t, uint32_t, uint32_t, uint64_t, uint32_t,
                                                uint4, const typename A::T*, const uint2*) {}
 };
@@ -621,10 +644,16 @@ banded_gotoh_score_kernel(const GotohParams p, const QA qa)
     constexpr bool QUAL = IsQual<QA>::value;
     constexpr int SH = (TYPE == NVBIO_HIP_LOCAL) ? 5 : 0;      // LOCAL carries scores x32 (see header)
     __shared__ T s_lut[QUAL ? 256 : 1];
+    constexpr bool TAB = A::TABLE && !QUAL;  // no qualities: s_masks[q] is the finished table of pattern symbol q, built here once per workgroup
     __shared__ uint2 s_masks[16];            // table arithmetic: which halves of the row's {lo, hi} hold the match score, by pattern symbol
     if (A::TABLE && threadIdx.x < 16u)
-        s_masks[threadIdx.x] = make_uint2(threadIdx.x == 0u ? 0x0000FFFFu : threadIdx.x == 1u ? 0xFFFF0000u : 0u,
-                                          threadIdx.x == 2u ? 0x0000FFFFu : threadIdx.x == 3u ? 0xFFFF0000u : 0u);
+    {
+        const uint2 m = make_uint2(threadIdx.x == 0u ? 0x0000FFFFu : threadIdx.x == 1u ? 0xFFFF0000u : 0u,
+                                   threadIdx.x == 2u ? 0x0000FFFFu : threadIdx.x == 3u ? 0xFFFF0000u : 0u);
+        const uint32_t mm = (uint32_t(A::cnst((p.match - p.gap_open) * (1 << SH))) & 0xFFFFu) * 0x10001u;
+        const uint32_t xx = (uint32_t(A::cnst((p.mismatch - p.gap_open) * (1 << SH))) & 0xFFFFu) * 0x10001u;
+        s_masks[threadIdx.x] = TAB ? make_uint2((mm & m.x) | (xx & ~m.x), (mm & m.y) | (xx & ~m.y)) : m;
+    }
     if (A::TABLE && !QUAL) __syncthreads();
     extern __shared__ __attribute__((aligned(16))) uint32_t s_stage[];    // [stage_pw + stage_tw][256]
     fill_lut<A>(s_lut, qa, p.gap_open, SH);
@@ -687,6 +716,7 @@ banded_gotoh_score_kernel(const GotohParams p, const QA qa)
         k.bytes = (p.pat.s.bits == 8u);
         k.sMM = (uint32_t(k.sM) & 0xFFFFu) * 0x10001u; k.sXX = (uint32_t(k.sX) & 0xFFFFu) * 0x10001u;
         const T infimum = k.inf;
+        k.pin();
 
         DPState<BAND, A> st;
         // init_row_zero (:46-77), stored as H + G_o (row frame: H + G_o - G_e)
@@ -722,7 +752,7 @@ banded_gotoh_score_kernel(const GotohParams p, const QA qa)
             // a block none of whose rows lets a symbol past the text's end into the band runs on table arithmetic
             // (the block's last row that exists: rows past the pattern's end are skipped, so they need no symbol)
             if (A::TABLE && (i0 + BT::ROWS < M ? i0 + BT::ROWS : M) - 1u + BAND - 1u < N)
-                RowUnrollN<BAND, TYPE, A, QUAL, true, 0, BT::ROWS>::run(st, k, i0, M, N, P, Tx, Q, s_lut, s_masks);
+                RowUnrollN<BAND, TYPE, A, QUAL, true, 0, BT::ROWS, TAB>::run(st, k, i0, M, N, P, Tx, Q, s_lut, s_masks);
             else
                 RowUnrollN<BAND, TYPE, A, QUAL, false, 0, BT::ROWS>::run(st, k, i0, M, N, P, Tx, Q, s_lut, s_masks);
             ring_advance<BAND, A>(st);
