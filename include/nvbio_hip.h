@@ -959,7 +959,7 @@ void nvbio_hip_comm_set_transport(const nvbio_hip_comm_transport* transport);
 
 /* Test switches.  A few named integers select alternative executions of the same results, for the parity suite to cover both
  * (NVBIO_HIP_FORCE_32BIT, NVBIO_HIP_NO_STAGING, NVBIO_HIP_FULL_GENERIC, NVBIO_HIP_FULL_SINGLE_JOB, NVBIO_HIP_FULL_ROWS, NVBIO_HIP_ED_SWEEP,
- * NVBIO_HIP_SELECT_LANES, NVBIO_HIP_TRACEBACK_LANES).  Each is seeded ONCE per process from the environment variable of the same name and
+ * NVBIO_HIP_SELECT_LANES, NVBIO_HIP_TRACEBACK_LANES, NVBIO_HIP_BANDED_PAIR).  Each is seeded ONCE per process from the environment variable of the same name and
  * changed afterwards only through nvbio_hip_set_test_switch (atomic; safe while other threads are inside library calls -- a call in flight
  * uses the value it read when it started).  0 = the default execution.  Production code leaves them alone. */
 int nvbio_hip_set_test_switch(const char* name, int value);     /* hipErrorInvalidValue for an unknown name */
@@ -987,6 +987,7 @@ const char* nvbio_hip_test_switch_name(int index);              /* the index-th 
 int         nvbio_hip_abi_version(void);
 const char* nvbio_hip_arch(void);           /* "gfx950" */
 const char* nvbio_hip_last_kernel(void);    /* name of the last kernel variant launched by this thread */
+const char* nvbio_hip_last_kernel_detail(void);  /* "pair" if that launch was the banded 16-bit LOCAL kernel in its two-jobs-per-lane form, else "" */
 
 #ifdef __cplusplus
 }

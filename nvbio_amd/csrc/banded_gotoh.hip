@@ -37,6 +37,7 @@
 //    Both produce the reference's int32 results bit for bit.
 //
 #include "banded_gotoh_bounded.h"
+#include "banded_gotoh_pair.h"
 #include <mutex>
 #include <unordered_map>
 #include <atomic>
@@ -48,6 +49,7 @@
 namespace nvb {
 
 thread_local const char* g_last_kernel = "";
+thread_local const char* g_last_pair = nullptr;
 
 #define NVB_DECL(B) \
     extern template hipError_t launch_band_width<B, NoQual>(const GotohParams&, const NoQual&, int, bool, hipStream_t); \
@@ -62,6 +64,8 @@ NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
     extern template hipError_t launch_band_width_bounded<B, QualArgs>(const GotohParams&, const QualArgs&, const BoundArgs&, int, bool, hipStream_t);
 NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
 #undef NVB_DECL
+
+extern template hipError_t launch_band_pair<15>(const GotohParams&, hipStream_t);
 
 template <typename QA>
 static hipError_t launch_bounded(const GotohParams& p, const QA& qa, const BoundArgs& ba, int type, uint32_t band, bool width16, hipStream_t s)
@@ -125,14 +129,31 @@ static uint32_t max_len_16bit(int32_t match, int32_t best_pair /* max substituti
     return lim <= 0 ? 0u : uint32_t(lim);
 }
 
+// The two-jobs-per-lane form of the 16-bit LOCAL kernel (banded_gotoh_pair.h) holds the same row frame as unsigned halves, plus
+// BIAS = 32 (|G_o - G_e| + |G_e|) <= 448: its largest value is BIAS + 32 * M * (S + |G_e|) + 30 <= 448 + 32 * 1022 + 30 = 33182 at
+// M = lim16, and the largest constant added to a half is a substitution byte (255) -- half of the unsigned range is left over, so lim16
+// is its limit too.  What it needs besides: fixed-length strings, no row that sees a symbol past the text's end (N >= M + BAND - 1: the
+// compare form is not built), scores that fit the byte table (0 <= mismatch - G_o, max(match, mismatch) - G_o <= 7, so that
+// (s - G_o) * 32 <= 255), and G_o <= G_e <= 0, so that S = h + (G_o - G_e) and E + G_e are subtractions of magnitudes.
+static bool pair_admitted(const GotohParams& p, int type, uint32_t band, uint32_t lim16)
+{
+    if (test_switch(SW_BANDED_PAIR) == 1 || type != NVBIO_HIP_LOCAL || band != 15u) return false;
+    if (p.pat.length || p.txt.length || p.n_dev || p.out_index || p.gate) return false;
+    const uint32_t M = p.pat.fixed_length, N = p.txt.fixed_length;
+    if (M == 0u || M > lim16 || uint64_t(N) < uint64_t(M) + band - 1u) return false;
+    if (p.gap_ext > 0 || p.gap_open > p.gap_ext) return false;
+    return p.mismatch >= p.gap_open && int64_t(std::max(p.match, p.mismatch)) - p.gap_open <= 7 && p.match >= p.gap_open;
+}
+
 } // namespace nvb
 
 template <typename QA>
 static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_abs_cost, int32_t best_pair, int32_t type, uint32_t band_len,
                                  const nvbio_hip_string_set* patterns, hipStream_t s, const char* tag16, const char* tag32, const bool views = false,
-                                 const nvb::BoundArgs* bound = nullptr, const bool asym = false)
+                                 const nvb::BoundArgs* bound = nullptr, const bool asym = false, const bool plain_entry = false)
 {
     using namespace nvb;
+    g_last_pair = nullptr;
     // NVBIO_HIP_FORCE_32BIT=1 disables the 16-bit kernels (used by the tests to cover both widths)
     // the row-frame kernels' limit (the plain launch); the limit of the recurrence as written (asymmetric costs, the bounded form -- and LOCAL jobs
     // between the two limits, which the plain launch hands to the A16P instance)
@@ -170,6 +191,10 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
         return launch_bounded<QA>(p, qa, *bound, type, band_len, width16, s);
     };
     p.plain16 = 0u;
+    if (plain_entry && pair_admitted(p, type, band_len, lim16)) {
+        g_last_kernel = g_last_pair = tag16;
+        return launch_band_pair<15>(p, s);
+    }
     if (lim16 > 0 && (!fixed || patterns->fixed_length <= lim16)) {
         p.len_lo = 0; p.len_hi = lim16;
         g_last_kernel = tag16;
@@ -231,7 +256,7 @@ NVB_API int nvbio_hip_banded_gotoh_score(
     p.stage_pw = max_pattern_len; p.stage_tw = 0;       // the hint, consumed by banded_gotoh_dispatch
     const int64_t A = std::max(std::max(iabs64(scheme->match), iabs64(scheme->mismatch)), std::max(iabs64(scheme->gap_open), iabs64(scheme->gap_ext)));
     return banded_gotoh_dispatch(p, NoQual(), A, std::max(scheme->match, scheme->mismatch), type, band_len, patterns, to_stream(stream),
-                                 "banded_gotoh_score_kernel<A16>", "banded_gotoh_score_kernel<A32>");
+                                 "banded_gotoh_score_kernel<A16>", "banded_gotoh_score_kernel<A32>", false, nullptr, false, true);
 }
 
 NVB_API int nvbio_hip_banded_gotoh_score_qual(
@@ -599,7 +624,8 @@ NVB_API int nvbio_hip_stream_destroy(void* stream)
 namespace nvb {
 static std::atomic<int> g_switch[SW_COUNT];
 static const char* const g_switch_name[SW_COUNT] = { "NVBIO_HIP_FORCE_32BIT", "NVBIO_HIP_NO_STAGING", "NVBIO_HIP_FULL_GENERIC", "NVBIO_HIP_ED_SWEEP",
-                                                     "NVBIO_HIP_FULL_SINGLE_JOB", "NVBIO_HIP_FULL_ROWS", "NVBIO_HIP_TRACEBACK_LANES", "NVBIO_HIP_SELECT_LANES" };
+                                                     "NVBIO_HIP_FULL_SINGLE_JOB", "NVBIO_HIP_FULL_ROWS", "NVBIO_HIP_TRACEBACK_LANES", "NVBIO_HIP_SELECT_LANES",
+                                                     "NVBIO_HIP_BANDED_PAIR" };
 static void seed_switches()
 {
     static std::once_flag once;
@@ -650,3 +676,4 @@ NVB_API int nvbio_hip_host_free(void* ptr) { return ptr ? hipHostFree(ptr) : hip
 NVB_API int         nvbio_hip_abi_version(void) { return NVBIO_HIP_ABI_VERSION; }
 NVB_API const char* nvbio_hip_arch(void)        { return "gfx950"; }
 NVB_API const char* nvbio_hip_last_kernel(void) { return nvb::g_last_kernel; }
+NVB_API const char* nvbio_hip_last_kernel_detail(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? "pair" : ""; }

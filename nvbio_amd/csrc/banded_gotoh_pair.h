@@ -1,0 +1,215 @@
+// banded_gotoh_pair.h -- the 16-bit LOCAL banded Gotoh score with TWO jobs per lane (no qualities, fixed-length strings).
+//
+// The row-frame recurrence of A16 (banded_gotoh_impl.h: A32::cell_rt has the derivation), with job A's value in bits 0-15 of every state
+// register and job B's in bits 16-31.  Both halves are UNSIGNED numbers: the row frame plus one constant BIAS.  Then
+//   * an add or subtract of a constant is one 32-bit op on c * 0x10001, as long as no half carries or borrows;
+//   * only the maxima need a packed instruction (v_pk_max_u16);
+//   * one v_perm_b32 delivers both jobs' substitution scores, which fit a byte each.
+//
+// Range.  With G = 32 |G_e|, D = 32 (G_e - G_o) >= 0 (the host admits G_o <= G_e <= 0 only) and S+ = max(match, mismatch, 0), row i holds
+//   zero  Z_i = BIAS + (i + 1) G                 h  in [Z_i, BIAS + 32 (i + 1) (S+ + |G_e|)]       key = h + j, j <= 30
+//   S = h - D >= Z_i - D                         E = max(E, S) - G >= Z_i - D - G                  diag = S(i-1) + sub, 0 <= sub <= 255
+// and the band starts at S(-1) = BIAS - D.  BIAS = D + G keeps every minuend at or above what is taken from it (Z_i - D - G >= 0,
+// S(-1) >= 0; the sink fold takes Z_i from a key >= Z_i).  The host admits 7 >= match - G_o, so D + G <= 448; with the row-frame limit
+// M (S+ + |G_e|) <= 1022 (max_len_16bit) the largest value is 448 + 32 * 1022 + 30 = 33182, and 255 more still fit 16 bits: the limit
+// of the signed kernel carries over unchanged.
+//
+// The infimum.  The reference's infimum stands in F of row -1 and in F[BAND-1] of every row.  In LOCAL every H is >= 0, so every real
+// S = H + G_o - G_e (in any row's frame) lies far above it -- and F only ever meets it next to a real S: F(i,j) = max(F(i-1,j+1),
+// S(i-1,j+1)).  E never sees it (E starts from the row's own S).  So the infimum never wins a maximum, and the frame's lowest value,
+// 0, takes its place: max(0, S) = S.
+#pragma once
+#include "banded_gotoh_impl.h"
+
+namespace nvb {
+
+struct P16 {
+    static __device__ __forceinline__ uint32_t rep(int32_t c)               { return (uint32_t(c) & 0xFFFFu) * 0x10001u; }
+    static __device__ __forceinline__ uint32_t mx(uint32_t a, uint32_t b)   { uint32_t r; asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+    // both jobs' text symbols of one band column as one byte selector: {g_A, zero, 4 + g_B, zero} picks entry g_A of tlo and g_B of thi
+    static constexpr uint32_t SEL_BASE = 0x0C040C00u;
+    static __device__ __forceinline__ uint32_t subst(uint32_t tlo, uint32_t thi, uint32_t sel) { return __builtin_amdgcn_perm(thi, tlo, sel); }
+
+    // one interior cell of both jobs (A16::cell_rt's block).  The serial chain per cell is E -> h -> S -> E (max, sub, max, sub); F, the
+    // diagonal and the row's zero are folded before E joins.  EDGE: the cell next to the band's edge, whose F(i-1,j+1) is the infimum.
+    template <int J, bool EDGE>
+    static __device__ __forceinline__ void cell(uint32_t& Fj, const uint32_t Fnext, const uint32_t Snext, uint32_t& Sj, uint32_t& E, uint32_t& rowkey,
+                                                const uint32_t g, const uint32_t D, const uint32_t G, const uint32_t tlo, const uint32_t thi, const uint32_t Z)
+    {
+        uint32_t d, h;
+        if (EDGE)
+            asm("v_perm_b32 %[d], %[thi], %[tlo], %[g]\n\t"
+                "v_mov_b32 %[f], %[sn]\n\t"
+                "v_add_u32 %[d], %[s], %[d]\n\t"
+                "v_pk_max_u16 %[h], %[sn], %[z]\n\t"
+                "v_pk_max_u16 %[h], %[h], %[d]\n\t"
+                "v_pk_max_u16 %[h], %[h], %[e]\n\t"
+                "v_sub_u32 %[s], %[h], %[dd]\n\t"
+                "v_add_u32 %[d], %[sj], %[h]\n\t"
+                "v_pk_max_u16 %[e], %[e], %[s]\n\t"
+                "v_sub_u32 %[e], %[e], %[gg]\n\t"
+                "v_pk_max_u16 %[rk], %[rk], %[d]"
+                : [f] "=&v"(Fj), [d] "=&v"(d), [h] "=&v"(h), [s] "+v"(Sj), [e] "+v"(E), [rk] "+v"(rowkey)
+                : [g] "v"(g), [tlo] "v"(tlo), [thi] "v"(thi), [sn] "v"(Snext), [dd] "v"(D), [gg] "v"(G), [z] "v"(Z), [sj] "n"(J * 0x10001));
+        else
+            asm("v_perm_b32 %[d], %[thi], %[tlo], %[g]\n\t"
+                "v_pk_max_u16 %[f], %[fn], %[sn]\n\t"
+                "v_add_u32 %[d], %[s], %[d]\n\t"
+                "v_pk_max_u16 %[h], %[f], %[z]\n\t"
+                "v_pk_max_u16 %[h], %[h], %[d]\n\t"
+                "v_pk_max_u16 %[h], %[h], %[e]\n\t"
+                "v_sub_u32 %[s], %[h], %[dd]\n\t"
+                "v_add_u32 %[d], %[sj], %[h]\n\t"
+                "v_pk_max_u16 %[e], %[e], %[s]\n\t"
+                "v_sub_u32 %[e], %[e], %[gg]\n\t"
+                "v_pk_max_u16 %[rk], %[rk], %[d]"
+                : [f] "=&v"(Fj), [d] "=&v"(d), [h] "=&v"(h), [s] "+v"(Sj), [e] "+v"(E), [rk] "+v"(rowkey)
+                : [g] "v"(g), [tlo] "v"(tlo), [thi] "v"(thi), [fn] "v"(Fnext), [sn] "v"(Snext), [dd] "v"(D), [gg] "v"(G), [z] "v"(Z), [sj] "n"(J * 0x10001));
+    }
+};
+
+template <int BAND>
+struct PairState {
+    uint32_t S[BAND];        // S = H' + G_o - G_e of the previous row, both jobs
+    uint32_t F[BAND - 1];
+    uint32_t tc[16];         // the band's text symbols, as selectors (a ring indexed by (row + column) & 15, like BandTraits)
+    uint32_t z;              // the row's zero
+    uint32_t best[2], besti[2];   // per job: the best key so far (score * 32 + j) and its row
+};
+
+template <int BAND, int R, int J, int END>
+struct PairCells {
+    static __device__ __forceinline__ void run(PairState<BAND>& st, uint32_t& E, uint32_t& rowkey, const uint32_t D, const uint32_t G, const uint32_t tlo, const uint32_t thi)
+    {
+        P16::cell<J, J + 1 == BAND - 1>(st.F[J], st.F[J + 1 < BAND - 1 ? J + 1 : 0], st.S[J + 1], st.S[J], E, rowkey, st.tc[(R + J) & 15], D, G, tlo, thi, st.z);
+        PairCells<BAND, R, J + 1, END>::run(st, E, rowkey, D, G, tlo, thi);
+    }
+};
+template <int BAND, int R, int END>
+struct PairCells<BAND, R, END, END> {
+    static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t&, uint32_t&, uint32_t, uint32_t, uint32_t, uint32_t) {}
+};
+
+// row i0 + R of both jobs.  g_new: the entering text symbols' selector; {tlo, thi}: the row's table, four byte entries per job
+template <int BAND, int R>
+__device__ __forceinline__ void pair_row(PairState<BAND>& st, const uint32_t i, const uint32_t D, const uint32_t G, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
+{
+    st.z += G;                                                                     // this row's zero
+    // j == 0
+    st.F[0] = (1 == BAND - 1) ? st.S[1] : P16::mx(st.F[1 < BAND - 1 ? 1 : 0], st.S[1]);
+    uint32_t hi = P16::mx(P16::mx(st.F[0], st.S[0] + P16::subst(tlo, thi, st.tc[R & 15])), st.z);
+    uint32_t rowkey = hi;
+    st.S[0] = hi - D;
+    uint32_t E = st.S[0] - G;
+    // 1 <= j <= BAND-2
+    PairCells<BAND, R, 1, BAND - 1>::run(st, E, rowkey, D, G, tlo, thi);
+    st.tc[(R + BAND - 1) & 15] = g_new;
+    // j == BAND-1
+    hi = P16::mx(P16::mx(E, st.S[BAND - 1] + P16::subst(tlo, thi, g_new)), st.z);
+    rowkey = P16::mx(rowkey, hi + uint32_t(BAND - 1) * 0x10001u);
+    st.S[BAND - 1] = hi - D;
+    // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here
+    rowkey -= st.z;
+    const uint32_t rk[2] = { rowkey & 0xFFFFu, rowkey >> 16 };
+    #pragma unroll
+    for (int h = 0; h < 2; ++h)
+    {
+        const bool upd = (rk[h] | 31u) >= st.best[h];
+        st.best[h]  = upd ? rk[h] : st.best[h];
+        st.besti[h] = upd ? i : st.besti[h];
+    }
+}
+
+template <int BAND, int R, int END>
+struct PairRows {
+    // XT[0] / XT[1]: the block's entering text symbols 0-7 / 8-15, job A's in the low half and job B's in the high half
+    static __device__ __forceinline__ void run(PairState<BAND>& st, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
+                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab)
+    {
+        if (i0 + R < M)
+        {
+            const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | P16::SEL_BASE;
+            pair_row<BAND, R>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
+        }
+        PairRows<BAND, R + 1, END>::run(st, i0, M, D, G, PA, PB, XT, tab);
+    }
+};
+template <int BAND, int END> struct PairRows<BAND, END, END> {
+    static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*) {}
+};
+
+// Lane k of the launch takes jobs 2k and 2k + 1 (with an odd n the last lane computes its one job in both halves).  The host has
+// checked (banded_gotoh.hip: pair_admitted) that every job has M >= 1 rows, that no row sees a symbol past the text's end and that the
+// scheme's scores fit the byte table.  The strings are read from HBM per 16-row block: staging them in LDS as banded_gotoh_score_kernel
+// does (two slots per lane) measured no faster with 256 lanes and slower with 128 (profiles/banded_pair/README.md), so there is none.
+constexpr int PAIR_LANES = 128;
+template <int BAND>
+__global__ void __launch_bounds__(PAIR_LANES)
+banded_gotoh_pair_kernel(const GotohParams p)
+{
+    static_assert(BAND >= 3 && BAND <= 16, "the ring of 16");
+    __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
+    if (threadIdx.x < 16u)
+    {
+        const uint32_t sm = uint32_t((p.match - p.gap_open) * 32), sx = uint32_t((p.mismatch - p.gap_open) * 32);
+        uint32_t t = sx * 0x01010101u;
+        if (threadIdx.x < 4u) t = (t & ~(0xFFu << (8u * threadIdx.x))) | (sm << (8u * threadIdx.x));
+        s_tab[threadIdx.x] = t;
+    }
+    __syncthreads();
+    const uint32_t lane = blockIdx.x * uint32_t(PAIR_LANES) + threadIdx.x;
+    if (lane >= p.n / 2u + (p.n & 1u)) return;
+    const uint32_t id[2] = { 2u * lane, 2u * lane + 1u < p.n ? 2u * lane + 1u : 2u * lane };
+    const uint32_t M = p.pat.fixed_length;
+    const Stream ps[2] = { p.pat.s, p.pat.s }, ts[2] = { p.txt.s, p.txt.s };
+    const uint64_t pb[2] = { p.pat.begin[id[0]], p.pat.begin[id[1]] }, tb[2] = { p.txt.begin[id[0]], p.txt.begin[id[1]] };
+
+    const int32_t d32 = (p.gap_ext - p.gap_open) * 32, g32 = -p.gap_ext * 32;
+    uint32_t D = P16::rep(d32), G = P16::rep(g32);
+    asm("" : "+v"(D)); asm("" : "+v"(G));                                         // resident, like A16::pin
+
+    PairState<BAND> st;
+    #pragma unroll
+    for (int j = 0; j < BAND; ++j) st.S[j] = P16::rep(g32);                        // H = 0 in row -1: BIAS - D
+    #pragma unroll
+    for (int j = 0; j < BAND - 1; ++j) st.F[j] = 0u;
+    st.z = P16::rep(d32 + g32);                                                   // BIAS
+    st.best[0] = st.best[1] = 0u; st.besti[0] = st.besti[1] = 0u;
+    {
+        const uint32_t TA = fetch16_2bit(ts[0], tb[0]), TB = fetch16_2bit(ts[1], tb[1]);
+        #pragma unroll
+        for (int j = 0; j < BAND - 1; ++j)
+            st.tc[j] = P16::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
+    }
+
+    uint64_t PA = fetch_pattern16(ps[0], pb[0]), PB = fetch_pattern16(ps[1], pb[1]);
+    uint32_t TA = fetch16_2bit(ts[0], tb[0] + BAND - 1), TB = fetch16_2bit(ts[1], tb[1] + BAND - 1);
+    for (uint32_t i0 = 0; i0 < M; i0 += 16u)
+    {
+        // prefetch the next block's symbols while this one computes
+        const uint64_t PAn = fetch_pattern16(ps[0], pb[0] + i0 + 16u), PBn = fetch_pattern16(ps[1], pb[1] + i0 + 16u);
+        const uint32_t TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1), TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
+        const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
+        PairRows<BAND, 0, 16>::run(st, i0, M, D, G, PA, PB, XT, s_tab);
+        PA = PAn; PB = PBn; TA = TAn; TB = TBn;
+    }
+
+    #pragma unroll
+    for (int h = 0; h < 2; ++h)
+    {
+        if (h == 1 && id[1] == id[0]) break;
+        const uint32_t j = st.best[h] & 31u;
+        p.out_score[id[h]] = int32_t(st.best[h] >> 5);
+        reinterpret_cast<uint2*>(p.out_sink)[id[h]] = make_uint2(st.besti[h] + j + 1u, st.besti[h] + 1u);
+    }
+}
+
+template <int BAND>
+hipError_t launch_band_pair(const GotohParams& p, hipStream_t stream)
+{
+    const uint32_t n_lanes = p.n / 2u + (p.n & 1u);
+    hipLaunchKernelGGL((banded_gotoh_pair_kernel<BAND>), dim3((n_lanes + PAIR_LANES - 1u) / PAIR_LANES), dim3(PAIR_LANES), 0, stream, p);
+    return hipGetLastError();
+}
+
+} // namespace nvb
