@@ -988,6 +988,7 @@ int         nvbio_hip_abi_version(void);
 const char* nvbio_hip_arch(void);           /* "gfx950" */
 const char* nvbio_hip_last_kernel(void);    /* name of the last kernel variant launched by this thread */
 const char* nvbio_hip_last_kernel_detail(void);  /* "pair" if that launch was the banded 16-bit LOCAL kernel in its two-jobs-per-lane form, else "" */
+const char* nvbio_hip_last_kernel_cell(void);    /* the cell of a "pair" launch: "max3" (three-input maxima) or "u16" (two-input ones), else "" */
 
 #ifdef __cplusplus
 }

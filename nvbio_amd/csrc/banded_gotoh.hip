@@ -50,6 +50,7 @@ namespace nvb {
 
 thread_local const char* g_last_kernel = "";
 thread_local const char* g_last_pair = nullptr;
+thread_local const char* g_last_pair_cell = "";
 
 #define NVB_DECL(B) \
     extern template hipError_t launch_band_width<B, NoQual>(const GotohParams&, const NoQual&, int, bool, hipStream_t); \
@@ -65,7 +66,8 @@ NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
 NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
 #undef NVB_DECL
 
-extern template hipError_t launch_band_pair<15>(const GotohParams&, hipStream_t);
+extern template hipError_t launch_band_pair<15, P16>(const GotohParams&, hipStream_t);
+extern template hipError_t launch_band_pair<15, PM3>(const GotohParams&, hipStream_t);
 
 template <typename QA>
 static hipError_t launch_bounded(const GotohParams& p, const QA& qa, const BoundArgs& ba, int type, uint32_t band, bool width16, hipStream_t s)
@@ -135,6 +137,7 @@ static uint32_t max_len_16bit(int32_t match, int32_t best_pair /* max substituti
 // is its limit too.  What it needs besides: fixed-length strings, no row that sees a symbol past the text's end (N >= M + BAND - 1: the
 // compare form is not built), scores that fit the byte table (0 <= mismatch - G_o, max(match, mismatch) - G_o <= 7, so that
 // (s - G_o) * 32 <= 255), and G_o <= G_e <= 0, so that S = h + (G_o - G_e) and E + G_e are subtractions of magnitudes.
+// NVBIO_HIP_BANDED_PAIR: 0 = the pair form where admitted, 1 = never, 2 = the pair form with the u16 cell only.
 static bool pair_admitted(const GotohParams& p, int type, uint32_t band, uint32_t lim16)
 {
     if (test_switch(SW_BANDED_PAIR) == 1 || type != NVBIO_HIP_LOCAL || band != 15u) return false;
@@ -143,6 +146,18 @@ static bool pair_admitted(const GotohParams& p, int type, uint32_t band, uint32_
     if (M == 0u || M > lim16 || uint64_t(N) < uint64_t(M) + band - 1u) return false;
     if (p.gap_ext > 0 || p.gap_open > p.gap_ext) return false;
     return p.mismatch >= p.gap_open && int64_t(std::max(p.match, p.mismatch)) - p.gap_open <= 7 && p.match >= p.gap_open;
+}
+
+// The max3 cell of the pair form (banded_gotoh_pair.h: PM3) takes its maxima with v_pk_maximum3_f16, which is an exact unsigned maximum
+// only while every half is a positive normal f16 pattern, 0x0400 ... 0x7BFF.  Its frame is raised by 0x0400, so its largest operand is
+// 0x0400 + BIAS + 32 * M * (S + |G_e|) + 255 (a diagonal: the substitution byte on top of a previous row's value; the keys add less).
+// With the largest BIAS pair_admitted lets through, 448, that is M * (S + |G_e|) <= (31743 - 255 - 1024 - 448) / 32 = 938
+// (PM3_ROW_LIMIT): M <= 312 for (2,-1,-2,-1), where the u16 cell goes on to lim16 = 340.
+static bool pair_max3_admitted(const GotohParams& p)
+{
+    if (test_switch(SW_BANDED_PAIR) == 2) return false;
+    const int64_t per_row = int64_t(std::max(std::max(p.match, p.mismatch), 0)) - p.gap_ext;
+    return int64_t(p.pat.fixed_length) * per_row <= PM3_ROW_LIMIT;
 }
 
 } // namespace nvb
@@ -154,6 +169,7 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
 {
     using namespace nvb;
     g_last_pair = nullptr;
+    g_last_pair_cell = "";
     // NVBIO_HIP_FORCE_32BIT=1 disables the 16-bit kernels (used by the tests to cover both widths)
     // the row-frame kernels' limit (the plain launch); the limit of the recurrence as written (asymmetric costs, the bounded form -- and LOCAL jobs
     // between the two limits, which the plain launch hands to the A16P instance)
@@ -193,7 +209,9 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
     p.plain16 = 0u;
     if (plain_entry && pair_admitted(p, type, band_len, lim16)) {
         g_last_kernel = g_last_pair = tag16;
-        return launch_band_pair<15>(p, s);
+        const bool max3 = pair_max3_admitted(p);
+        g_last_pair_cell = max3 ? "max3" : "u16";
+        return max3 ? launch_band_pair<15, PM3>(p, s) : launch_band_pair<15, P16>(p, s);
     }
     if (lim16 > 0 && (!fixed || patterns->fixed_length <= lim16)) {
         p.len_lo = 0; p.len_hi = lim16;
@@ -677,3 +695,4 @@ NVB_API int         nvbio_hip_abi_version(void) { return NVBIO_HIP_ABI_VERSION; 
 NVB_API const char* nvbio_hip_arch(void)        { return "gfx950"; }
 NVB_API const char* nvbio_hip_last_kernel(void) { return nvb::g_last_kernel; }
 NVB_API const char* nvbio_hip_last_kernel_detail(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? "pair" : ""; }
+NVB_API const char* nvbio_hip_last_kernel_cell(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_cell : ""; }

@@ -18,17 +18,72 @@
 // S = H + G_o - G_e (in any row's frame) lies far above it -- and F only ever meets it next to a real S: F(i,j) = max(F(i-1,j+1),
 // S(i-1,j+1)).  E never sees it (E starts from the row's own S).  So the infimum never wins a maximum, and the frame's lowest value,
 // 0, takes its place: max(0, S) = S.
+//
+// Two cells.  P16 is the cell above: two-input v_pk_max_u16 throughout, six per interior cell.  PM3 takes the same maxima three at a
+// time with v_pk_maximum3_f16 (gfx950).  For bit patterns in 0x0400 ... 0x7BFF -- the positive normal halves -- the order of f16 is the
+// order of the unsigned 16-bit patterns, there is no NaN, infinity or subnormal among them, and a maximum returns one of its operands
+// unchanged: over that range the instruction IS an exact packed three-input unsigned maximum (and v_pk_max_u16 agrees with it, so the
+// two mix freely).  PM3 keeps every operand of every maximum inside the range:
+//   * the frame is raised by FLOOR = 0x0400: BIAS' = D + G + 0x0400, S(-1) = BIAS' - D = G + 0x0400, and F starts at the frame's lowest
+//     value 0x0400 in place of 0.  Every bound of "Range" moves up by 0x0400 with it: the smallest value any register holds is
+//     E >= Z_i - D - G = 0x0400 + i G >= 0x0400, and S, z, diag, h, F, key and the row key lie above it.
+//   * no carry, no borrow, as before with 0x0400 to spare: S = h - D with h >= Z_i >= BIAS' > D;  E = max(E, S) - G with
+//     S >= Z_i - D = 0x0400 + (i + 2) G > G;  the sink fold takes Z_i from a row key >= h(i,0) >= Z_i;  the adds (z + G, S + sub,
+//     h + j) stay at or below the top, which is below 2^15.
+//   * the top: the largest operand is a diagonal, S(i-1) + sub <= BIAS' + 32 M (S+ + |G_e|) + 255 (a key adds j <= 14 to an h instead),
+//     and must not pass 0x7BFF = 31743.  With the largest BIAS the byte table admits, D + G = 448, that is
+//     32 M (S+ + |G_e|) <= 31743 - 255 - 1024 - 448 = 30016, M (S+ + |G_e|) <= 938 (PM3_ROW_LIMIT; the host's pair_admitted sends longer
+//     jobs, up to the 1022 of P16, to P16).
+// What the three-input form buys:
+//   * F' = max(F, Z_i), the zero clamp folded into F:  F'(i,j) = max3(F'(i-1,j+1), S(i-1,j+1), Z_i).  The row's zero never falls
+//     (Z_(i-1) <= Z_i, equal when G_e = 0), so by induction on i, with F'(-1,.) = 0x0400 <= Z_0:
+//       F'(i,j) = max(max(F(i-1,j+1), Z_(i-1)), S(i-1,j+1), Z_i) = max(F(i-1,j+1), S(i-1,j+1), Z_i) = max(F(i,j), Z_i),
+//     and h = max3(F', diag, E) = max(F, Z_i, diag, E) is the h of P16: two instructions where P16 has four.  Next to the band's edge
+//     F' = max(S(i-1,j+1), Z_i); column 0 (no E) takes h = max(F', diag); the last column (no F) takes h = max3(E, diag, Z_i).
+//   * the row key takes two columns' keys at a time: rowkey = max3(rowkey, key_j, key_(j+1)).
+//   * E = max(E, S) stays a two-input maximum.
+// An interior cell is then 8.5 vector instructions, 3.5 of them maxima, where P16 has 11 and 6.
 #pragma once
 #include "banded_gotoh_impl.h"
 
 namespace nvb {
 
-struct P16 {
+template <int BAND>
+struct PairState {
+    uint32_t S[BAND];        // S = H' + G_o - G_e of the previous row, both jobs
+    uint32_t F[BAND - 1];
+    uint32_t tc[16];         // the band's text symbols, as selectors (a ring indexed by (row + column) & 15, like BandTraits)
+    uint32_t z;              // the row's zero
+    uint32_t best[2], besti[2];   // per job: the best key so far (score * 32 + j) and its row
+};
+
+// what both cells share: the replicated constants, the substitution lookup and the sink
+struct PairOps {
     static __device__ __forceinline__ uint32_t rep(int32_t c)               { return (uint32_t(c) & 0xFFFFu) * 0x10001u; }
     static __device__ __forceinline__ uint32_t mx(uint32_t a, uint32_t b)   { uint32_t r; asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
     // both jobs' text symbols of one band column as one byte selector: {g_A, zero, 4 + g_B, zero} picks entry g_A of tlo and g_B of thi
     static constexpr uint32_t SEL_BASE = 0x0C040C00u;
     static __device__ __forceinline__ uint32_t subst(uint32_t tlo, uint32_t thi, uint32_t sel) { return __builtin_amdgcn_perm(thi, tlo, sel); }
+
+    // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here
+    template <int BAND>
+    static __device__ __forceinline__ void sink(PairState<BAND>& st, uint32_t rowkey, const uint32_t i)
+    {
+        rowkey -= st.z;
+        const uint32_t rk[2] = { rowkey & 0xFFFFu, rowkey >> 16 };
+        #pragma unroll
+        for (int h = 0; h < 2; ++h)
+        {
+            const bool upd = (rk[h] | 31u) >= st.best[h];
+            st.best[h]  = upd ? rk[h] : st.best[h];
+            st.besti[h] = upd ? i : st.besti[h];
+        }
+    }
+};
+
+// ---- the u16 cell: two-input maxima, the frame's lowest value is 0
+struct P16 : PairOps {
+    static constexpr int32_t FLOOR = 0;
 
     // one interior cell of both jobs (A16::cell_rt's block).  The serial chain per cell is E -> h -> S -> E (max, sub, max, sub); F, the
     // diagonal and the row's zero are folded before E joins.  EDGE: the cell next to the band's edge, whose F(i-1,j+1) is the infimum.
@@ -66,61 +121,137 @@ struct P16 {
                 : [f] "=&v"(Fj), [d] "=&v"(d), [h] "=&v"(h), [s] "+v"(Sj), [e] "+v"(E), [rk] "+v"(rowkey)
                 : [g] "v"(g), [tlo] "v"(tlo), [thi] "v"(thi), [fn] "v"(Fnext), [sn] "v"(Snext), [dd] "v"(D), [gg] "v"(G), [z] "v"(Z), [sj] "n"(J * 0x10001));
     }
-};
 
-template <int BAND>
-struct PairState {
-    uint32_t S[BAND];        // S = H' + G_o - G_e of the previous row, both jobs
-    uint32_t F[BAND - 1];
-    uint32_t tc[16];         // the band's text symbols, as selectors (a ring indexed by (row + column) & 15, like BandTraits)
-    uint32_t z;              // the row's zero
-    uint32_t best[2], besti[2];   // per job: the best key so far (score * 32 + j) and its row
-};
+    template <int BAND, int R, int J, int END>
+    struct Cells {
+        static __device__ __forceinline__ void run(PairState<BAND>& st, uint32_t& E, uint32_t& rowkey, const uint32_t D, const uint32_t G, const uint32_t tlo, const uint32_t thi)
+        {
+            cell<J, J + 1 == BAND - 1>(st.F[J], st.F[J + 1 < BAND - 1 ? J + 1 : 0], st.S[J + 1], st.S[J], E, rowkey, st.tc[(R + J) & 15], D, G, tlo, thi, st.z);
+            Cells<BAND, R, J + 1, END>::run(st, E, rowkey, D, G, tlo, thi);
+        }
+    };
+    template <int BAND, int R, int END>
+    struct Cells<BAND, R, END, END> {
+        static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t&, uint32_t&, uint32_t, uint32_t, uint32_t, uint32_t) {}
+    };
 
-template <int BAND, int R, int J, int END>
-struct PairCells {
-    static __device__ __forceinline__ void run(PairState<BAND>& st, uint32_t& E, uint32_t& rowkey, const uint32_t D, const uint32_t G, const uint32_t tlo, const uint32_t thi)
+    // row i0 + R of both jobs.  g_new: the entering text symbols' selector; {tlo, thi}: the row's table, four byte entries per job
+    template <int BAND, int R>
+    static __device__ __forceinline__ void row(PairState<BAND>& st, const uint32_t i, const uint32_t D, const uint32_t G, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
     {
-        P16::cell<J, J + 1 == BAND - 1>(st.F[J], st.F[J + 1 < BAND - 1 ? J + 1 : 0], st.S[J + 1], st.S[J], E, rowkey, st.tc[(R + J) & 15], D, G, tlo, thi, st.z);
-        PairCells<BAND, R, J + 1, END>::run(st, E, rowkey, D, G, tlo, thi);
+        st.z += G;                                                                     // this row's zero
+        // j == 0
+        st.F[0] = (1 == BAND - 1) ? st.S[1] : mx(st.F[1 < BAND - 1 ? 1 : 0], st.S[1]);
+        uint32_t hi = mx(mx(st.F[0], st.S[0] + subst(tlo, thi, st.tc[R & 15])), st.z);
+        uint32_t rowkey = hi;
+        st.S[0] = hi - D;
+        uint32_t E = st.S[0] - G;
+        // 1 <= j <= BAND-2
+        Cells<BAND, R, 1, BAND - 1>::run(st, E, rowkey, D, G, tlo, thi);
+        st.tc[(R + BAND - 1) & 15] = g_new;
+        // j == BAND-1
+        hi = mx(mx(E, st.S[BAND - 1] + subst(tlo, thi, g_new)), st.z);
+        rowkey = mx(rowkey, hi + uint32_t(BAND - 1) * 0x10001u);
+        st.S[BAND - 1] = hi - D;
+        sink(st, rowkey, i);
     }
 };
-template <int BAND, int R, int END>
-struct PairCells<BAND, R, END, END> {
-    static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t&, uint32_t&, uint32_t, uint32_t, uint32_t, uint32_t) {}
+
+// ---- the max3 cell: three-input maxima on halves kept inside the positive normal f16 patterns (the header comment has the argument)
+constexpr int32_t PM3_ROW_LIMIT = (0x7BFF - 255 - 0x0400 - 448) / 32;             // 938 >= M (S+ + |G_e|)
+struct PM3 : PairOps {
+    static constexpr int32_t FLOOR = 0x0400;
+    static __device__ __forceinline__ uint32_t mx3(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
+
+    // the interior cells J and J + 1 of both jobs, neither next to the band's edge.  F2 / S2: F'(i-1,J+2) and S(i-1,J+2).  F1 and S1 are
+    // read as the previous row's (cell J's F', cell J + 1's diagonal) before cell J + 1 overwrites them.  The serial chain per cell is
+    // E -> h -> S -> E as in P16 (max3, sub, max, sub); both F' and both diagonals are ready before E joins.
+    template <int J>
+    static __device__ __forceinline__ void cell2(uint32_t& F0, uint32_t& F1, const uint32_t F2, uint32_t& S0, uint32_t& S1, const uint32_t S2, uint32_t& E, uint32_t& rowkey,
+                                                 const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t G, const uint32_t tlo, const uint32_t thi, const uint32_t Z)
+    {
+        uint32_t d0, d1, h;
+        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
+            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z]\n\t"
+            "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z]\n\t"
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[e]\n\t"
+            "v_sub_u32 %[s0], %[h], %[dd]\n\t"
+            "v_add_u32 %[d0], %[j0], %[h]\n\t"
+            "v_pk_max_u16 %[e], %[e], %[s0]\n\t"
+            "v_sub_u32 %[e], %[e], %[gg]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f1], %[d1], %[e]\n\t"
+            "v_sub_u32 %[s1], %[h], %[dd]\n\t"
+            "v_add_u32 %[d1], %[j1], %[h]\n\t"
+            "v_pk_max_u16 %[e], %[e], %[s1]\n\t"
+            "v_sub_u32 %[e], %[e], %[gg]\n\t"
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+            : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "+&v"(E), [rk] "+&v"(rowkey)
+            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [dd] "v"(D), [gg] "v"(G), [z] "v"(Z),
+              [j0] "n"(J * 0x10001), [j1] "n"((J + 1) * 0x10001));
+    }
+
+    // the cell J next to the band's edge (F(i-1,J+1) is the infimum: F' = max(S(i-1,J+1), Z)) and the last column J + 1 (no F:
+    // h = max3(E, diagonal, Z))
+    template <int J>
+    static __device__ __forceinline__ void tail2(uint32_t& F0, uint32_t& S0, uint32_t& S1, uint32_t& E, uint32_t& rowkey,
+                                                 const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t G, const uint32_t tlo, const uint32_t thi, const uint32_t Z)
+    {
+        uint32_t d0, d1, h;
+        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
+            "v_pk_max_u16 %[f0], %[s1], %[z]\n\t"
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[e]\n\t"
+            "v_sub_u32 %[s0], %[h], %[dd]\n\t"
+            "v_add_u32 %[d0], %[j0], %[h]\n\t"
+            "v_pk_max_u16 %[e], %[e], %[s0]\n\t"
+            "v_sub_u32 %[e], %[e], %[gg]\n\t"
+            "v_pk_maximum3_f16 %[h], %[e], %[d1], %[z]\n\t"
+            "v_sub_u32 %[s1], %[h], %[dd]\n\t"
+            "v_add_u32 %[d1], %[j1], %[h]\n\t"
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+            : [f0] "=&v"(F0), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "+&v"(E), [rk] "+&v"(rowkey)
+            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [dd] "v"(D), [gg] "v"(G), [z] "v"(Z),
+              [j0] "n"(J * 0x10001), [j1] "n"((J + 1) * 0x10001));
+    }
+
+    template <int BAND, int R, int J, int END>
+    struct Cells {
+        static __device__ __forceinline__ void run(PairState<BAND>& st, uint32_t& E, uint32_t& rowkey, const uint32_t D, const uint32_t G, const uint32_t tlo, const uint32_t thi)
+        {
+            cell2<J>(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], E, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], D, G, tlo, thi, st.z);
+            Cells<BAND, R, J + 2, END>::run(st, E, rowkey, D, G, tlo, thi);
+        }
+    };
+    template <int BAND, int R, int END>
+    struct Cells<BAND, R, END, END> {
+        static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t&, uint32_t&, uint32_t, uint32_t, uint32_t, uint32_t) {}
+    };
+
+    template <int BAND, int R>
+    static __device__ __forceinline__ void row(PairState<BAND>& st, const uint32_t i, const uint32_t D, const uint32_t G, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
+    {
+        static_assert(BAND % 2 == 1, "columns 1 ... BAND-3 go two at a time");
+        st.z += G;                                                                     // this row's zero
+        // j == 0: no E
+        st.F[0] = (1 == BAND - 1) ? mx(st.S[1], st.z) : mx3(st.F[1 < BAND - 1 ? 1 : 0], st.S[1], st.z);
+        const uint32_t hi = mx(st.F[0], st.S[0] + subst(tlo, thi, st.tc[R & 15]));
+        uint32_t rowkey = hi;
+        st.S[0] = hi - D;
+        uint32_t E = st.S[0] - G;
+        // 1 <= j <= BAND-3, then BAND-2 and BAND-1
+        Cells<BAND, R, 1, BAND - 2>::run(st, E, rowkey, D, G, tlo, thi);
+        st.tc[(R + BAND - 1) & 15] = g_new;
+        tail2<BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, D, G, tlo, thi, st.z);
+        sink(st, rowkey, i);
+    }
 };
 
-// row i0 + R of both jobs.  g_new: the entering text symbols' selector; {tlo, thi}: the row's table, four byte entries per job
-template <int BAND, int R>
-__device__ __forceinline__ void pair_row(PairState<BAND>& st, const uint32_t i, const uint32_t D, const uint32_t G, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
-{
-    st.z += G;                                                                     // this row's zero
-    // j == 0
-    st.F[0] = (1 == BAND - 1) ? st.S[1] : P16::mx(st.F[1 < BAND - 1 ? 1 : 0], st.S[1]);
-    uint32_t hi = P16::mx(P16::mx(st.F[0], st.S[0] + P16::subst(tlo, thi, st.tc[R & 15])), st.z);
-    uint32_t rowkey = hi;
-    st.S[0] = hi - D;
-    uint32_t E = st.S[0] - G;
-    // 1 <= j <= BAND-2
-    PairCells<BAND, R, 1, BAND - 1>::run(st, E, rowkey, D, G, tlo, thi);
-    st.tc[(R + BAND - 1) & 15] = g_new;
-    // j == BAND-1
-    hi = P16::mx(P16::mx(E, st.S[BAND - 1] + P16::subst(tlo, thi, g_new)), st.z);
-    rowkey = P16::mx(rowkey, hi + uint32_t(BAND - 1) * 0x10001u);
-    st.S[BAND - 1] = hi - D;
-    // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here
-    rowkey -= st.z;
-    const uint32_t rk[2] = { rowkey & 0xFFFFu, rowkey >> 16 };
-    #pragma unroll
-    for (int h = 0; h < 2; ++h)
-    {
-        const bool upd = (rk[h] | 31u) >= st.best[h];
-        st.best[h]  = upd ? rk[h] : st.best[h];
-        st.besti[h] = upd ? i : st.besti[h];
-    }
-}
-
-template <int BAND, int R, int END>
+template <typename CELL, int BAND, int R, int END>
 struct PairRows {
     // XT[0] / XT[1]: the block's entering text symbols 0-7 / 8-15, job A's in the low half and job B's in the high half
     static __device__ __forceinline__ void run(PairState<BAND>& st, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
@@ -128,22 +259,22 @@ struct PairRows {
     {
         if (i0 + R < M)
         {
-            const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | P16::SEL_BASE;
-            pair_row<BAND, R>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
+            const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
+            CELL::template row<BAND, R>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
         }
-        PairRows<BAND, R + 1, END>::run(st, i0, M, D, G, PA, PB, XT, tab);
+        PairRows<CELL, BAND, R + 1, END>::run(st, i0, M, D, G, PA, PB, XT, tab);
     }
 };
-template <int BAND, int END> struct PairRows<BAND, END, END> {
+template <typename CELL, int BAND, int END> struct PairRows<CELL, BAND, END, END> {
     static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*) {}
 };
 
 // Lane k of the launch takes jobs 2k and 2k + 1 (with an odd n the last lane computes its one job in both halves).  The host has
 // checked (banded_gotoh.hip: pair_admitted) that every job has M >= 1 rows, that no row sees a symbol past the text's end and that the
-// scheme's scores fit the byte table.  The strings are read from HBM per 16-row block: staging them in LDS as banded_gotoh_score_kernel
+// scheme's scores fit the byte table, and for CELL = PM3 that M (S+ + |G_e|) <= PM3_ROW_LIMIT.  The strings are read from HBM per 16-row block: staging them in LDS as banded_gotoh_score_kernel
 // does (two slots per lane) measured no faster with 256 lanes and slower with 128 (profiles/banded_pair/README.md), so there is none.
 constexpr int PAIR_LANES = 128;
-template <int BAND>
+template <int BAND, typename CELL>
 __global__ void __launch_bounds__(PAIR_LANES)
 banded_gotoh_pair_kernel(const GotohParams p)
 {
@@ -165,21 +296,21 @@ banded_gotoh_pair_kernel(const GotohParams p)
     const uint64_t pb[2] = { p.pat.begin[id[0]], p.pat.begin[id[1]] }, tb[2] = { p.txt.begin[id[0]], p.txt.begin[id[1]] };
 
     const int32_t d32 = (p.gap_ext - p.gap_open) * 32, g32 = -p.gap_ext * 32;
-    uint32_t D = P16::rep(d32), G = P16::rep(g32);
+    uint32_t D = CELL::rep(d32), G = CELL::rep(g32);
     asm("" : "+v"(D)); asm("" : "+v"(G));                                         // resident, like A16::pin
 
     PairState<BAND> st;
     #pragma unroll
-    for (int j = 0; j < BAND; ++j) st.S[j] = P16::rep(g32);                        // H = 0 in row -1: BIAS - D
+    for (int j = 0; j < BAND; ++j) st.S[j] = CELL::rep(g32 + CELL::FLOOR);          // H = 0 in row -1: BIAS - D
     #pragma unroll
-    for (int j = 0; j < BAND - 1; ++j) st.F[j] = 0u;
-    st.z = P16::rep(d32 + g32);                                                   // BIAS
+    for (int j = 0; j < BAND - 1; ++j) st.F[j] = CELL::rep(CELL::FLOOR);
+    st.z = CELL::rep(d32 + g32 + CELL::FLOOR);                                     // BIAS
     st.best[0] = st.best[1] = 0u; st.besti[0] = st.besti[1] = 0u;
     {
         const uint32_t TA = fetch16_2bit(ts[0], tb[0]), TB = fetch16_2bit(ts[1], tb[1]);
         #pragma unroll
         for (int j = 0; j < BAND - 1; ++j)
-            st.tc[j] = P16::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
+            st.tc[j] = CELL::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
     }
 
     uint64_t PA = fetch_pattern16(ps[0], pb[0]), PB = fetch_pattern16(ps[1], pb[1]);
@@ -190,7 +321,7 @@ banded_gotoh_pair_kernel(const GotohParams p)
         const uint64_t PAn = fetch_pattern16(ps[0], pb[0] + i0 + 16u), PBn = fetch_pattern16(ps[1], pb[1] + i0 + 16u);
         const uint32_t TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1), TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
         const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
-        PairRows<BAND, 0, 16>::run(st, i0, M, D, G, PA, PB, XT, s_tab);
+        PairRows<CELL, BAND, 0, 16>::run(st, i0, M, D, G, PA, PB, XT, s_tab);
         PA = PAn; PB = PBn; TA = TAn; TB = TBn;
     }
 
@@ -204,11 +335,11 @@ banded_gotoh_pair_kernel(const GotohParams p)
     }
 }
 
-template <int BAND>
+template <int BAND, typename CELL>
 hipError_t launch_band_pair(const GotohParams& p, hipStream_t stream)
 {
     const uint32_t n_lanes = p.n / 2u + (p.n & 1u);
-    hipLaunchKernelGGL((banded_gotoh_pair_kernel<BAND>), dim3((n_lanes + PAIR_LANES - 1u) / PAIR_LANES), dim3(PAIR_LANES), 0, stream, p);
+    hipLaunchKernelGGL((banded_gotoh_pair_kernel<BAND, CELL>), dim3((n_lanes + PAIR_LANES - 1u) / PAIR_LANES), dim3(PAIR_LANES), 0, stream, p);
     return hipGetLastError();
 }
 

@@ -12,6 +12,8 @@ namespace nvb {
 extern thread_local const char* g_last_kernel;
 // the g_last_kernel value of the last launch that took the two-jobs-per-lane form (banded_gotoh_pair.h), or NULL: nvbio_hip_last_kernel_detail
 extern thread_local const char* g_last_pair;
+// which cell that launch ran, "u16" or "max3": nvbio_hip_last_kernel_cell
+extern thread_local const char* g_last_pair_cell;
 
 // Test switches (include/nvbio_hip.h, "Test switches"): alternative executions of the same results.  Each is an atomic int, seeded ONCE
 // from the environment variable of the same name (std::call_once) and changed afterwards only through nvbio_hip_set_test_switch --

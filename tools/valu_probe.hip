@@ -83,7 +83,16 @@
   X(add_i16,      "v_add_i16 %0, %0, %1") \
   X(max_i16_e64,  "v_max_i16_e64 %0, %0, %1") \
   X(mov_b32,      "v_mov_b32 %0, %1") \
-  X(swap_b32,     "v_swap_b32 %0, %1")
+  X(swap_b32,     "v_swap_b32 %0, %1") \
+  X(pk_max_u16,   "v_pk_max_u16 %0, %0, %1") \
+  X(pk_max_f16,   "v_pk_max_f16 %0, %0, %1") \
+  X(pk_maximum3_f16, "v_pk_maximum3_f16 %0, %0, %1, %1") \
+  X(pk_minimum3_f16, "v_pk_minimum3_f16 %0, %0, %1, %1") \
+  X(add_u32_lit,  "v_add_u32 %0, 0x000d000d, %0") \
+  X(pk_add_u16,   "v_pk_add_u16 %0, %0, %1") \
+  X(max3_then_u16,"v_pk_maximum3_f16 %0, %0, %1, %1\n v_pk_max_u16 %0, %0, %1") \
+  X(max3_then_sub,"v_pk_maximum3_f16 %0, %0, %1, %1\n v_sub_u32 %0, %0, %1") \
+  X(u16_then_sub, "v_pk_max_u16 %0, %0, %1\n v_sub_u32 %0, %0, %1")
 
 #define X(name, str) \
 __global__ void __launch_bounds__(256) k_##name(uint32_t* out, int iters) { \
