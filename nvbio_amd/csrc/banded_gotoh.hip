@@ -51,6 +51,7 @@ namespace nvb {
 thread_local const char* g_last_kernel = "";
 thread_local const char* g_last_pair = nullptr;
 thread_local const char* g_last_pair_cell = "";
+thread_local const char* g_last_pair_fetch = "";
 
 #define NVB_DECL(B) \
     extern template hipError_t launch_band_width<B, NoQual>(const GotohParams&, const NoQual&, int, bool, hipStream_t); \
@@ -66,8 +67,11 @@ NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
 NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
 #undef NVB_DECL
 
-extern template hipError_t launch_band_pair<15, P16>(const GotohParams&, hipStream_t);
-extern template hipError_t launch_band_pair<15, PM3>(const GotohParams&, hipStream_t);
+#define NVB_DECL(F) \
+    extern template hipError_t launch_band_pair<15, P16, (F)>(const GotohParams&, hipStream_t); \
+    extern template hipError_t launch_band_pair<15, PM3, (F)>(const GotohParams&, hipStream_t);
+NVB_DECL(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_DECL)
+#undef NVB_DECL
 
 template <typename QA>
 static hipError_t launch_bounded(const GotohParams& p, const QA& qa, const BoundArgs& ba, int type, uint32_t band, bool width16, hipStream_t s)
@@ -148,6 +152,27 @@ static bool pair_admitted(const GotohParams& p, int type, uint32_t band, uint32_
     return p.mismatch >= p.gap_open && int64_t(std::max(p.match, p.mismatch)) - p.gap_open <= 7 && p.match >= p.gap_open;
 }
 
+// The pair form's block loop streams its words through 32-bit byte offsets (common.h: GroupStream) where the pattern has 2 or 4 bits
+// and neither word array comes near 2^32 bytes; an 8-bit pattern or a longer array keeps the generic fetches.  The streamed kernel
+// has the pattern's width and both byte orders as template parameters: launch_pair picks the instance.
+static bool pair_stream_admitted(const GotohParams& p)
+{
+    return p.pat.s.bits != 8u && p.pat.s.n_words <= (1ull << 29) && p.txt.s.n_words <= (1ull << 29);
+}
+template <typename CELL>
+static hipError_t launch_pair(const GotohParams& p, hipStream_t s)
+{
+    g_last_pair_fetch = "generic";
+    if (!pair_stream_admitted(p)) return launch_band_pair<15, CELL, PF_SINK_VCC>(p, s);
+    g_last_pair_fetch = "stream";
+    switch (PF_STREAM | (p.pat.s.bits == 2u ? PF_PAT2 : 0) | (p.pat.s.big_endian ? PF_PBE : 0) | (p.txt.s.big_endian ? PF_TBE : 0)) {
+#define NVB_CASE(F) case (F): return launch_band_pair<15, CELL, (F)>(p, s);
+    NVB_PAIR_STREAM_FORMS(NVB_CASE)
+#undef NVB_CASE
+    }
+    return hipErrorNotSupported;
+}
+
 // The max3 cell of the pair form (banded_gotoh_pair.h: PM3) takes its maxima with v_pk_maximum3_f16, which is an exact unsigned maximum
 // only while every half is a positive normal f16 pattern, 0x0400 ... 0x7BFF.  Its frame is raised by 0x0400, so its largest operand is
 // 0x0400 + BIAS + 32 * M * (S + |G_e|) + 255 (a diagonal: the substitution byte on top of a previous row's value; the keys add less).
@@ -170,6 +195,7 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
     using namespace nvb;
     g_last_pair = nullptr;
     g_last_pair_cell = "";
+    g_last_pair_fetch = "";
     // NVBIO_HIP_FORCE_32BIT=1 disables the 16-bit kernels (used by the tests to cover both widths)
     // the row-frame kernels' limit (the plain launch); the limit of the recurrence as written (asymmetric costs, the bounded form -- and LOCAL jobs
     // between the two limits, which the plain launch hands to the A16P instance)
@@ -211,7 +237,7 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
         g_last_kernel = g_last_pair = tag16;
         const bool max3 = pair_max3_admitted(p);
         g_last_pair_cell = max3 ? "max3" : "u16";
-        return max3 ? launch_band_pair<15, PM3>(p, s) : launch_band_pair<15, P16>(p, s);
+        return max3 ? launch_pair<PM3>(p, s) : launch_pair<P16>(p, s);
     }
     if (lim16 > 0 && (!fixed || patterns->fixed_length <= lim16)) {
         p.len_lo = 0; p.len_hi = lim16;
@@ -695,4 +721,5 @@ NVB_API int         nvbio_hip_abi_version(void) { return NVBIO_HIP_ABI_VERSION; 
 NVB_API const char* nvbio_hip_arch(void)        { return "gfx950"; }
 NVB_API const char* nvbio_hip_last_kernel(void) { return nvb::g_last_kernel; }
 NVB_API const char* nvbio_hip_last_kernel_detail(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? "pair" : ""; }
+NVB_API const char* nvbio_hip_last_kernel_fetch(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_fetch : ""; }
 NVB_API const char* nvbio_hip_last_kernel_cell(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_cell : ""; }

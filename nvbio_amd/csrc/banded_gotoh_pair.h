@@ -43,6 +43,16 @@
 //   * the row key takes two columns' keys at a time: rowkey = max3(rowkey, key_j, key_(j+1)).
 //   * E = max(E, S) stays a two-input maximum.
 // An interior cell is then 8.5 vector instructions, 3.5 of them maxima, where P16 has 11 and 6.
+//
+// The sink.  Un-framed (its row's zero taken off), a job's row key is p = score * 32 + j: the row's best score and the largest column
+// that holds it, 16 bits.  The fold's rule is "replace when (p | 31) >= best": the higher score wins, and on an equal score the later
+// row.  The library folds it with a compare and two selects per job (PF_SINK_VCC), the key in one register and its row in another.
+// PF_SINK_KEY, which only tools/pair_row_probe.hip launches, folds one 32-bit key per job with a plain unsigned maximum instead:
+//     W = p << 15 | 31 << 15 | i << 5 | (p & 31),     best = max(best, W),
+// score in bits 20-29, the copy of j that the shift leaves in bits 15-19 saturated to a constant, the row i in bits 5-14, j in bits
+// 0-4.  Unsigned order on W is the order of (score, row, column), and every row folds a different i, so the maximum over the rows is
+// the fold's result; the epilogue decodes score = W >> 20, i = (W >> 5) & 1023, j = W & 31.  It needs score <= 1023 and i <= 1023,
+// three instructions fewer per row, and measured no faster (profiles/banded_pair/README.md), so the library does not take it.
 #pragma once
 #include "banded_gotoh_impl.h"
 
@@ -57,6 +67,21 @@ struct PairState {
     uint32_t best[2], besti[2];   // per job: the best key so far (score * 32 + j) and its row
 };
 
+// The kernel's forms, one template parameter.  The host picks the fetch (banded_gotoh.hip: launch_pair); the key sink and the
+// knock-outs exist for tools/pair_row_probe.hip alone, which times the row with one part taken out and its inputs kept live.  No
+// knock-out computes results.
+enum PairForm : int {
+    PF_SINK_VCC = 0, PF_SINK_KEY = 1,                                               // the sink fold: compare + select / one 32-bit key (probe only)
+    PF_STREAM   = 4,                                                                // the block loop streams its words (GroupStream, common.h), and then:
+    PF_PAT2     = 2,                                                                //   the pattern has 2 bits (else 4)
+    PF_PBE      = 8, PF_TBE = 256,                                                  //   the pattern's / the text's words are big-endian
+    PF_KO_SINK  = 16, PF_KO_TABLE = 32, PF_KO_FETCH = 64, PF_KO_BOUND = 128         // probe only
+};
+// the streamed forms the library holds: every pattern width and byte order it streams
+#define NVB_PAIR_STREAM_FORMS(X) \
+    X(PF_STREAM) X(PF_STREAM | PF_PBE) X(PF_STREAM | PF_TBE) X(PF_STREAM | PF_PBE | PF_TBE) \
+    X(PF_STREAM | PF_PAT2) X(PF_STREAM | PF_PAT2 | PF_PBE) X(PF_STREAM | PF_PAT2 | PF_TBE) X(PF_STREAM | PF_PAT2 | PF_PBE | PF_TBE)
+
 // what both cells share: the replicated constants, the substitution lookup and the sink
 struct PairOps {
     static __device__ __forceinline__ uint32_t rep(int32_t c)               { return (uint32_t(c) & 0xFFFFu) * 0x10001u; }
@@ -65,11 +90,31 @@ struct PairOps {
     static constexpr uint32_t SEL_BASE = 0x0C040C00u;
     static __device__ __forceinline__ uint32_t subst(uint32_t tlo, uint32_t thi, uint32_t sel) { return __builtin_amdgcn_perm(thi, tlo, sel); }
 
-    // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here
-    template <int BAND>
+    // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here.  The fold, the probe's key form of it
+    // (the header comment, "The sink") and the probe's knock-out, which keeps the row key live through one packed maximum
+    template <int FORM, int BAND>
     static __device__ __forceinline__ void sink(PairState<BAND>& st, uint32_t rowkey, const uint32_t i)
     {
         rowkey -= st.z;
+        if (FORM & PF_KO_SINK) { st.best[0] = mx(st.best[0], rowkey); return; }
+        if (FORM & PF_SINK_KEY)
+        {
+            // as C++ the compiler spends twelve instructions on it (an SDWA shift, the frame's two parts or-ed in one after the other),
+            // so the eight are written out
+            const uint32_t frame = (31u << 15) | (i << 5);                          // wave-uniform
+            uint32_t a, b, wa, wb;
+            asm("v_and_b32 %[a], 0xffff, %[rk]\n\t"
+                "v_lshrrev_b32 %[b], 16, %[rk]\n\t"
+                "v_lshl_or_b32 %[wa], %[a], 15, %[fr]\n\t"
+                "v_lshl_or_b32 %[wb], %[b], 15, %[fr]\n\t"
+                "v_and_or_b32 %[wa], %[a], 31, %[wa]\n\t"
+                "v_and_or_b32 %[wb], %[b], 31, %[wb]\n\t"
+                "v_max_u32 %[ba], %[ba], %[wa]\n\t"
+                "v_max_u32 %[bb], %[bb], %[wb]"
+                : [a] "=&v"(a), [b] "=&v"(b), [wa] "=&v"(wa), [wb] "=&v"(wb), [ba] "+&v"(st.best[0]), [bb] "+&v"(st.best[1])
+                : [rk] "v"(rowkey), [fr] "s"(frame));
+            return;
+        }
         const uint32_t rk[2] = { rowkey & 0xFFFFu, rowkey >> 16 };
         #pragma unroll
         for (int h = 0; h < 2; ++h)
@@ -136,7 +181,7 @@ struct P16 : PairOps {
     };
 
     // row i0 + R of both jobs.  g_new: the entering text symbols' selector; {tlo, thi}: the row's table, four byte entries per job
-    template <int BAND, int R>
+    template <int BAND, int R, int FORM>
     static __device__ __forceinline__ void row(PairState<BAND>& st, const uint32_t i, const uint32_t D, const uint32_t G, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
     {
         st.z += G;                                                                     // this row's zero
@@ -153,7 +198,7 @@ struct P16 : PairOps {
         hi = mx(mx(E, st.S[BAND - 1] + subst(tlo, thi, g_new)), st.z);
         rowkey = mx(rowkey, hi + uint32_t(BAND - 1) * 0x10001u);
         st.S[BAND - 1] = hi - D;
-        sink(st, rowkey, i);
+        sink<FORM>(st, rowkey, i);
     }
 };
 
@@ -232,7 +277,7 @@ struct PM3 : PairOps {
         static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t&, uint32_t&, uint32_t, uint32_t, uint32_t, uint32_t) {}
     };
 
-    template <int BAND, int R>
+    template <int BAND, int R, int FORM>
     static __device__ __forceinline__ void row(PairState<BAND>& st, const uint32_t i, const uint32_t D, const uint32_t G, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
     {
         static_assert(BAND % 2 == 1, "columns 1 ... BAND-3 go two at a time");
@@ -247,38 +292,45 @@ struct PM3 : PairOps {
         Cells<BAND, R, 1, BAND - 2>::run(st, E, rowkey, D, G, tlo, thi);
         st.tc[(R + BAND - 1) & 15] = g_new;
         tail2<BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, D, G, tlo, thi, st.z);
-        sink(st, rowkey, i);
+        sink<FORM>(st, rowkey, i);
     }
 };
 
-template <typename CELL, int BAND, int R, int END>
+template <typename CELL, int BAND, int FORM, int R, int END>
 struct PairRows {
     // XT[0] / XT[1]: the block's entering text symbols 0-7 / 8-15, job A's in the low half and job B's in the high half
+    // (KT: the resident table of the probe's PF_KO_TABLE, otherwise unused)
     static __device__ __forceinline__ void run(PairState<BAND>& st, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
-                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab)
+                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab, const uint32_t (&KT)[2])
     {
-        if (i0 + R < M)
+        if ((FORM & PF_KO_BOUND) || i0 + R < M)
         {
             const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
-            CELL::template row<BAND, R>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
+            if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, KT[0], KT[1]);
+            else                    CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
         }
-        PairRows<CELL, BAND, R + 1, END>::run(st, i0, M, D, G, PA, PB, XT, tab);
+        PairRows<CELL, BAND, FORM, R + 1, END>::run(st, i0, M, D, G, PA, PB, XT, tab, KT);
     }
 };
-template <typename CELL, int BAND, int END> struct PairRows<CELL, BAND, END, END> {
-    static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*) {}
+template <typename CELL, int BAND, int FORM, int END> struct PairRows<CELL, BAND, FORM, END, END> {
+    static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2]) {}
 };
 
 // Lane k of the launch takes jobs 2k and 2k + 1 (with an odd n the last lane computes its one job in both halves).  The host has
 // checked (banded_gotoh.hip: pair_admitted) that every job has M >= 1 rows, that no row sees a symbol past the text's end and that the
 // scheme's scores fit the byte table, and for CELL = PM3 that M (S+ + |G_e|) <= PM3_ROW_LIMIT.  The strings are read from HBM per 16-row block: staging them in LDS as banded_gotoh_score_kernel
 // does (two slots per lane) measured no faster with 256 lanes and slower with 128 (profiles/banded_pair/README.md), so there is none.
+// FORM & PF_STREAM: the host has also checked that both word arrays are short enough for GroupStream's 32-bit byte offsets and has
+// picked the instance of the pattern's width and the two byte orders (PF_PAT2, PF_PBE, PF_TBE), so the loop tests none of them; it
+// loads three new words per job and block where fetch16_* loads five.
 constexpr int PAIR_LANES = 128;
-template <int BAND, typename CELL>
+template <int BAND, typename CELL, int FORM>
 __global__ void __launch_bounds__(PAIR_LANES)
 banded_gotoh_pair_kernel(const GotohParams p)
 {
     static_assert(BAND >= 3 && BAND <= 16, "the ring of 16");
+    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0;
+    constexpr bool P4 = !(FORM & PF_PAT2), PBE = (FORM & PF_PBE) != 0, TBE = (FORM & PF_TBE) != 0;     // STREAM only: the host has matched them to the strings
     __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
     if (threadIdx.x < 16u)
     {
@@ -291,13 +343,15 @@ banded_gotoh_pair_kernel(const GotohParams p)
     const uint32_t lane = blockIdx.x * uint32_t(PAIR_LANES) + threadIdx.x;
     if (lane >= p.n / 2u + (p.n & 1u)) return;
     const uint32_t id[2] = { 2u * lane, 2u * lane + 1u < p.n ? 2u * lane + 1u : 2u * lane };
-    const uint32_t M = p.pat.fixed_length;
+    const uint32_t M = (FORM & PF_KO_BOUND) ? 96u : p.pat.fixed_length;
     const Stream ps[2] = { p.pat.s, p.pat.s }, ts[2] = { p.txt.s, p.txt.s };
     const uint64_t pb[2] = { p.pat.begin[id[0]], p.pat.begin[id[1]] }, tb[2] = { p.txt.begin[id[0]], p.txt.begin[id[1]] };
 
     const int32_t d32 = (p.gap_ext - p.gap_open) * 32, g32 = -p.gap_ext * 32;
     uint32_t D = CELL::rep(d32), G = CELL::rep(g32);
     asm("" : "+v"(D)); asm("" : "+v"(G));                                         // resident, like A16::pin
+    uint32_t KT[2] = { 0u, 0u };
+    if (FORM & PF_KO_TABLE) { KT[0] = s_tab[threadIdx.x & 3u]; KT[1] = s_tab[(threadIdx.x >> 2) & 3u]; asm("" : "+v"(KT[0])); asm("" : "+v"(KT[1])); }
 
     PairState<BAND> st;
     #pragma unroll
@@ -313,33 +367,74 @@ banded_gotoh_pair_kernel(const GotohParams p)
             st.tc[j] = CELL::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
     }
 
-    uint64_t PA = fetch_pattern16(ps[0], pb[0]), PB = fetch_pattern16(ps[1], pb[1]);
-    uint32_t TA = fetch16_2bit(ts[0], tb[0] + BAND - 1), TB = fetch16_2bit(ts[1], tb[1] + BAND - 1);
+    // this block's symbols and the cursors behind them (STREAM), or the generic fetches
+    const uint32_t plast = stream_last_off(p.pat.s), tlast = stream_last_off(p.txt.s);
+    GroupStream gp[2], gt[2];
+    uint64_t PA, PB;
+    uint32_t TA, TB;
+    if (STREAM)
+    {
+        if (P4) { PA = stream_open_4bit<PBE>(ps[0], plast, pb[0], gp[0]); PB = stream_open_4bit<PBE>(ps[1], plast, pb[1], gp[1]); }
+        else    { PA = expand_2to4(stream_open_2bit<PBE>(ps[0], plast, pb[0], gp[0])); PB = expand_2to4(stream_open_2bit<PBE>(ps[1], plast, pb[1], gp[1])); }
+        TA = stream_open_2bit<TBE>(ts[0], tlast, tb[0] + BAND - 1, gt[0]); TB = stream_open_2bit<TBE>(ts[1], tlast, tb[1] + BAND - 1, gt[1]);
+    }
+    else
+    {
+        PA = fetch_pattern16(ps[0], pb[0]); PB = fetch_pattern16(ps[1], pb[1]);
+        TA = fetch16_2bit(ts[0], tb[0] + BAND - 1); TB = fetch16_2bit(ts[1], tb[1] + BAND - 1);
+    }
     for (uint32_t i0 = 0; i0 < M; i0 += 16u)
     {
-        // prefetch the next block's symbols while this one computes
-        const uint64_t PAn = fetch_pattern16(ps[0], pb[0] + i0 + 16u), PBn = fetch_pattern16(ps[1], pb[1] + i0 + 16u);
-        const uint32_t TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1), TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
+        // the next block's symbols: loaded before this block's rows, put in order after them (STREAM), so that no wave sits waiting
+        // for its words with the rows still to do; the generic fetches finish their groups here
+        uint64_t PAn = 0, PBn = 0;
+        uint32_t TAn = 0, TBn = 0;
+        uint2 rp[2] = { make_uint2(0u, 0u), make_uint2(0u, 0u) };
+        uint32_t rt[2] = { 0u, 0u };
+        if (FORM & PF_KO_FETCH) {}
+        else if (STREAM)
+        {
+            if (P4) { rp[0] = stream_load_4bit(ps[0], plast, gp[0]); rp[1] = stream_load_4bit(ps[1], plast, gp[1]); }
+            else    { rp[0].x = stream_load_2bit(ps[0], plast, gp[0]); rp[1].x = stream_load_2bit(ps[1], plast, gp[1]); }
+            rt[0] = stream_load_2bit(ts[0], tlast, gt[0]); rt[1] = stream_load_2bit(ts[1], tlast, gt[1]);
+        }
+        else
+        {
+            PAn = fetch_pattern16(ps[0], pb[0] + i0 + 16u); PBn = fetch_pattern16(ps[1], pb[1] + i0 + 16u);
+            TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1); TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
+        }
         const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
-        PairRows<CELL, BAND, 0, 16>::run(st, i0, M, D, G, PA, PB, XT, s_tab);
-        PA = PAn; PB = PBn; TA = TAn; TB = TBn;
+        PairRows<CELL, BAND, FORM, 0, 16>::run(st, i0, M, D, G, PA, PB, XT, s_tab, KT);
+        if (FORM & PF_KO_FETCH)
+        {
+            PA = (PA << 4) | (PA >> 60); PB = (PB << 8) | (PB >> 56);
+            TA = funnel(TA, TA, 2u); TB = funnel(TB, TB, 6u);
+        }
+        else if (STREAM)
+        {
+            if (P4) { PA = stream_group_4bit<PBE>(gp[0], rp[0]); PB = stream_group_4bit<PBE>(gp[1], rp[1]); }
+            else    { PA = expand_2to4(stream_group_2bit<PBE>(gp[0], rp[0].x)); PB = expand_2to4(stream_group_2bit<PBE>(gp[1], rp[1].x)); }
+            TA = stream_group_2bit<TBE>(gt[0], rt[0]); TB = stream_group_2bit<TBE>(gt[1], rt[1]);
+        }
+        else { PA = PAn; PB = PBn; TA = TAn; TB = TBn; }
     }
 
     #pragma unroll
     for (int h = 0; h < 2; ++h)
     {
         if (h == 1 && id[1] == id[0]) break;
-        const uint32_t j = st.best[h] & 31u;
-        p.out_score[id[h]] = int32_t(st.best[h] >> 5);
-        reinterpret_cast<uint2*>(p.out_sink)[id[h]] = make_uint2(st.besti[h] + j + 1u, st.besti[h] + 1u);
+        // the key sink's best is score << 20 | 31 << 15 | row << 5 | column
+        const uint32_t j = st.best[h] & 31u, i = KEY ? (st.best[h] >> 5) & 1023u : st.besti[h];
+        p.out_score[id[h]] = int32_t(st.best[h] >> (KEY ? 20 : 5));
+        reinterpret_cast<uint2*>(p.out_sink)[id[h]] = make_uint2(i + j + 1u, i + 1u);
     }
 }
 
-template <int BAND, typename CELL>
+template <int BAND, typename CELL, int FORM>
 hipError_t launch_band_pair(const GotohParams& p, hipStream_t stream)
 {
     const uint32_t n_lanes = p.n / 2u + (p.n & 1u);
-    hipLaunchKernelGGL((banded_gotoh_pair_kernel<BAND, CELL>), dim3((n_lanes + PAIR_LANES - 1u) / PAIR_LANES), dim3(PAIR_LANES), 0, stream, p);
+    hipLaunchKernelGGL((banded_gotoh_pair_kernel<BAND, CELL, FORM>), dim3((n_lanes + PAIR_LANES - 1u) / PAIR_LANES), dim3(PAIR_LANES), 0, stream, p);
     return hipGetLastError();
 }
 

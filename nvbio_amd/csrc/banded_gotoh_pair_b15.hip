@@ -1,6 +1,9 @@
-// explicit instantiation: band 15, two jobs per lane, both cells
+// explicit instantiation: band 15, two jobs per lane, both cells; the generic fetches and every streamed form
 #include "banded_gotoh_pair.h"
 namespace nvb {
-template hipError_t launch_band_pair<15, P16>(const GotohParams&, hipStream_t);
-template hipError_t launch_band_pair<15, PM3>(const GotohParams&, hipStream_t);
+#define NVB_INST(F) \
+    template hipError_t launch_band_pair<15, P16, (F)>(const GotohParams&, hipStream_t); \
+    template hipError_t launch_band_pair<15, PM3, (F)>(const GotohParams&, hipStream_t);
+NVB_INST(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_INST)
+#undef NVB_INST
 }

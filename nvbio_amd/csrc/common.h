@@ -14,6 +14,8 @@ extern thread_local const char* g_last_kernel;
 extern thread_local const char* g_last_pair;
 // which cell that launch ran, "u16" or "max3": nvbio_hip_last_kernel_cell
 extern thread_local const char* g_last_pair_cell;
+// how its block loop read the strings, "stream" or "generic": nvbio_hip_last_kernel_fetch
+extern thread_local const char* g_last_pair_fetch;
 
 // Test switches (include/nvbio_hip.h, "Test switches"): alternative executions of the same results.  Each is an atomic int, seeded ONCE
 // from the environment variable of the same name (std::call_once) and changed afterwards only through nvbio_hip_set_test_switch --
@@ -89,7 +91,73 @@ __device__ __forceinline__ uint64_t fetch16_4bit(const Stream& s, uint64_t sym)
     const uint32_t lo = funnel(w0, w1, sh), hi = funnel(w1, w2, sh);
     return (uint64_t(hi) << 32) | lo;
 }
-// 16 symbols of an 8-bit stream as 16 nibbles.  The text is 2-bit, so all that matters of a pattern byte is WHICH text symbol it
+// ---- the same groups for a loop that walks one string 16 symbols at a time.  Consecutive groups share a word and the funnel shift
+// never changes, so a cursor carries that word, already in canonical order, and the next group loads only the words that are new: one
+// for a 2-bit stream, two for a 4-bit one.  The cursor is the BYTE offset of the carried word in 32 bits, clamped with one minimum
+// against the last word's (the caller has checked 4 * n_words + 8 < 2^32); every word is the one fetch16_* would have loaded -- word
+// min(k, n_words - 1) for each k on its own.  HBM only: a staged stream stays on fetch16_*.
+struct GroupStream {
+    uint32_t off;       // byte offset of the carried word
+    uint32_t carry;     // the last word read, canonical order
+    uint32_t sh;        // funnel shift
+};
+__device__ __forceinline__ uint32_t stream_last_off(const Stream& s) { return uint32_t(s.n_words - 1u) * 4u; }
+__device__ __forceinline__ uint32_t stream_raw(const Stream& s, uint32_t off) { return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(s.words) + off); }
+// BITS, BE: the stream's width and byte order, which the caller knows at compile time (they are not read from the Stream)
+template <int BITS, bool BE>
+__device__ __forceinline__ uint32_t canonical(uint32_t w) { return !BE ? w : BITS == 2 ? rev2(w) : rev4(w); }
+__device__ __forceinline__ uint32_t stream_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+// open at symbol `sym` and return its group
+template <bool BE>
+__device__ __forceinline__ uint32_t stream_open_2bit(const Stream& s, const uint32_t last, uint64_t sym, GroupStream& g)
+{
+    const uint64_t k = sym >> 4;
+    const uint32_t o0 = k < s.n_words ? uint32_t(k) * 4u : last;
+    g.off = stream_min(o0 + 4u, last); g.sh = (uint32_t(sym) & 15u) << 1;
+    const uint32_t w0 = canonical<2, BE>(stream_raw(s, o0));
+    g.carry = canonical<2, BE>(stream_raw(s, g.off));
+    return funnel(w0, g.carry, g.sh);
+}
+template <bool BE>
+__device__ __forceinline__ uint64_t stream_open_4bit(const Stream& s, const uint32_t last, uint64_t sym, GroupStream& g)
+{
+    const uint64_t k = sym >> 3;
+    const uint32_t o0 = k < s.n_words ? uint32_t(k) * 4u : last, o1 = stream_min(o0 + 4u, last);
+    g.off = stream_min(o0 + 8u, last); g.sh = (uint32_t(sym) & 7u) << 2;
+    const uint32_t w0 = canonical<4, BE>(stream_raw(s, o0)), w1 = canonical<4, BE>(stream_raw(s, o1));
+    g.carry = canonical<4, BE>(stream_raw(s, g.off));
+    return (uint64_t(funnel(w1, g.carry, g.sh)) << 32) | funnel(w0, w1, g.sh);
+}
+// The group 16 symbols after the last one returned, in two steps, so that a loop can put its work between them and nothing waits
+// for the loads: stream_load_* moves the cursor on and returns the new words as they are in memory; stream_group_* puts them into
+// canonical order and funnels the group out of the carried word and them.
+__device__ __forceinline__ uint32_t stream_load_2bit(const Stream& s, const uint32_t last, GroupStream& g)
+{
+    g.off = stream_min(g.off + 4u, last);
+    return stream_raw(s, g.off);
+}
+__device__ __forceinline__ uint2 stream_load_4bit(const Stream& s, const uint32_t last, GroupStream& g)
+{
+    const uint32_t o1 = stream_min(g.off + 4u, last);
+    g.off = stream_min(g.off + 8u, last);
+    return make_uint2(stream_raw(s, o1), stream_raw(s, g.off));
+}
+template <bool BE>
+__device__ __forceinline__ uint32_t stream_group_2bit(GroupStream& g, const uint32_t raw)
+{
+    const uint32_t w0 = g.carry;
+    g.carry = canonical<2, BE>(raw);
+    return funnel(w0, g.carry, g.sh);
+}
+template <bool BE>
+__device__ __forceinline__ uint64_t stream_group_4bit(GroupStream& g, const uint2 raw)
+{
+    const uint32_t w0 = g.carry, w1 = canonical<4, BE>(raw.x);
+    g.carry = canonical<4, BE>(raw.y);
+    return (uint64_t(funnel(w1, g.carry, g.sh)) << 32) | funnel(w0, w1, g.sh);
+}
+
+// 16 symbols of an 8-bit stream as 16 nibbles. The text is 2-bit, so all that matters of a pattern byte is WHICH text symbol it
 // equals, if any: 0..3 stay, 255 -- the value the reference compares a text position past the end as (gotoh_banded_inl.h:580) --
 // becomes 15, any other byte 4 (equal to nothing)
 __device__ __forceinline__ uint64_t fetch16_8bit(const Stream& s, uint64_t sym)
