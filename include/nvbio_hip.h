@@ -229,7 +229,11 @@ int nvbio_hip_banded_gotoh_score_qual_bounded(
  * (nvbio_hip_banded_gotoh_traceback_temp_bytes), which reproduces the reference for every interval
  * as long as the DP values fit its int16 checkpoints; schemes/lengths with
  * (max_pattern_len + band_len + 2) * max|cost| >= 32000 are refused with 801.
- * max_pattern_len is required for ragged pattern sets. */
+ * max_pattern_len is required for ragged pattern sets.
+ * Strings (all three entries, and nvbio_hip_banded_sw_traceback): patterns of 2, 4 or 8 bits, texts of 2 bits (else 801).  Of an 8-bit
+ * pattern's byte only which text symbol it equals matters: 0..3 are those symbols, 255 equals a text position past the end (the value the
+ * reference compares it as) and nothing else, every other byte equals nothing.  Quality bytes stay one per pattern symbol at the
+ * patterns' own offsets. */
 uint64_t nvbio_hip_banded_gotoh_traceback_temp_bytes(uint32_t band_len, uint32_t max_pattern_len, uint32_t n);
 int nvbio_hip_banded_gotoh_traceback(
     const nvbio_hip_gotoh_scheme* scheme /* host */, int32_t type, uint32_t band_len,
@@ -263,7 +267,9 @@ int nvbio_hip_banded_gotoh_traceback_qual_known(
  * :407-425, the walk of gotoh_inl.h:1806-1870 and the driver's completion along the first row / column (:443-466).
  * Outputs as nvbio_hip_banded_gotoh_traceback (source/sink: x = text position, y = pattern position).
  * The flow flags of the whole matrix live in `temp` (nvbio_hip_gotoh_traceback_temp_bytes: 4 bytes per 8 cells + 4 bytes
- * per text symbol, per job); CHECKPOINTS has no equivalent.  Requires the int16-exact range of the full-matrix scorer. */
+ * per text symbol, per job); CHECKPOINTS has no equivalent.  Requires the int16-exact range of the full-matrix scorer.
+ * Strings (this entry, the _qual and _known_score forms and nvbio_hip_sw_traceback): patterns of 2, 4 or 8 bits -- a byte other than
+ * 0..3 equals no text symbol --, texts of 2 bits (else 801). */
 uint64_t nvbio_hip_gotoh_traceback_temp_bytes(uint32_t max_pattern_len, uint32_t max_text_len, uint32_t n);
 int nvbio_hip_gotoh_traceback(
     const nvbio_hip_gotoh_scheme* scheme /* host */, int32_t type,
@@ -313,9 +319,13 @@ int nvbio_hip_gotoh_traceback_qual_known_score(
 
 uint64_t nvbio_hip_known_score_redone(void);     /* jobs the two forms above traced again since the library was loaded */
 
-/* The tracebacks for SmithWatermanAligner / EditDistanceAligner (deletion == insertion), banded (sw_banded_inl.h:405-470,
- * 748-800) and full matrix (sw_inl.h:389-396, 475-500, 1660-1700): arguments and temp sizes as the Gotoh forms.  The banded
- * reference context does not mark zero cells, so its LOCAL walk always reaches the first pattern row; reproduced. */
+/* The tracebacks for SmithWatermanAligner / EditDistanceAligner, banded (sw_banded_inl.h:405-470, 748-800) and full matrix
+ * (sw_inl.h:389-396, 475-500, 1660-1700): arguments, strings and temp sizes as the Gotoh forms.  deletion and insertion may differ, with
+ * the reference's convention for each matrix: in the band `deletion` is paid for the move from the previous pattern row (and on GLOBAL's
+ * row zero, j * deletion) and `insertion` along the row; in the full matrix `deletion` is paid along the text (the column before the
+ * pattern is deletion * (i + 1) for GLOBAL) and `insertion` down the pattern (the row before the text is insertion * j for non-LOCAL).
+ * The int16-range refusals (801) take the largest |cost| over all four.  The banded reference context does not mark zero cells, so its
+ * LOCAL walk always reaches the first pattern row; reproduced. */
 int nvbio_hip_banded_sw_traceback(
     const nvbio_hip_sw_scheme* scheme /* host */, int32_t type, uint32_t band_len,
     const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts,

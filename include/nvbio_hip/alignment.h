@@ -157,6 +157,14 @@ inline int full_score(const nvbio_hip_sw_scheme& sc, int32 type, const nvbio_hip
     if (e == 0 && ok && n) return nvbio_hip_memset(ok, 1, n, stream);
     return e;
 }
+inline void full_traceback(const nvbio_hip_gotoh_scheme& sc, int32 type, const nvbio_hip_string_set& p, const nvbio_hip_string_set& t,
+                          uint32 maxP, uint32 maxT, uint32 n, int32* score, uint32* sink, uint32* source,
+                          uint16* cigar, uint32 cigar_stride, uint32* cigar_len, void* temp, uint64 temp_size, void* stream)
+{ hip_check(nvbio_hip_gotoh_traceback(&sc, type, &p, &t, maxP, maxT, n, score, sink, source, cigar, cigar_stride, cigar_len, temp, temp_size, stream), "nvbio_hip_gotoh_traceback"); }
+inline void full_traceback(const nvbio_hip_sw_scheme& sc, int32 type, const nvbio_hip_string_set& p, const nvbio_hip_string_set& t,
+                          uint32 maxP, uint32 maxT, uint32 n, int32* score, uint32* sink, uint32* source,
+                          uint16* cigar, uint32 cigar_stride, uint32* cigar_len, void* temp, uint64 temp_size, void* stream)
+{ hip_check(nvbio_hip_sw_traceback(&sc, type, &p, &t, maxP, maxT, n, score, sink, source, cigar, cigar_stride, cigar_len, temp, temp_size, stream), "nvbio_hip_sw_traceback"); }
 struct int4_scheme { int32 v[4]; };
 inline int4_scheme scheme4(const SimpleGotohScheme& s) { const int4_scheme r = { { s.m_match, s.m_mismatch, s.m_gap_open, s.m_gap_ext } }; return r; }
 inline int4_scheme scheme4(const SimpleSmithWatermanScheme& s) { const int4_scheme r = { { s.m_match, s.m_mismatch, s.m_deletion, s.m_insertion } }; return r; }
@@ -358,6 +366,17 @@ private:
                       reinterpret_cast<uint16*>(stream.m_cigars.cigar), stream.m_cigars.cigar_stride, stream.m_cigars.cigar_len,
                       temp, temp_size, hip_stream), "nvbio_hip_banded_gotoh_traceback_qual");
     }
+    /// SmithWatermanAligner / EditDistanceAligner (whose scheme is the linear one with costs 0, -1, -1, -1); deletion and insertion may differ
+    static void call(const SimpleSmithWatermanScheme& scheme, stream_type& stream, uint64 temp_size, uint8* temp, void* hip_stream, bool)
+    {
+        const nvbio_hip_sw_scheme sc = priv::abi_scheme(scheme);
+        const nvbio_hip_string_set p = stream.m_patterns.abi(), t = stream.m_texts.abi();
+        hip_check(nvbio_hip_banded_sw_traceback(&sc, int32(aligner_type::TYPE), BAND_LEN, &p, &t,
+                      stream.max_pattern_length(), stream.max_text_length(), stream.size(),
+                      stream.m_alignments.score, stream.m_alignments.sink, stream.m_alignments.source,
+                      reinterpret_cast<uint16*>(stream.m_cigars.cigar), stream.m_cigars.cigar_stride, stream.m_cigars.cigar_len,
+                      temp, temp_size, hip_stream), "nvbio_hip_banded_sw_traceback");
+    }
 };
 
 /// BatchedAlignmentScore<stream, scheduler> (batched.h:310-329) for the full-matrix Gotoh score with
@@ -384,8 +403,9 @@ struct BatchedAlignmentScore
     }
 };
 
-/// BatchedAlignmentTraceback<CHECKPOINTS, stream, scheduler> (batched.h:432-452): full-matrix Gotoh traceback with
-/// nvBowtie's CIGAR-forming backtracer; the stream is the PackedTracebackStream of the banded form.
+/// BatchedAlignmentTraceback<CHECKPOINTS, stream, scheduler> (batched.h:432-452): full-matrix traceback with nvBowtie's
+/// CIGAR-forming backtracer for the Gotoh, Smith-Waterman and edit-distance aligners; the stream is the PackedTracebackStream
+/// of the banded form.
 template <uint32 CHECKPOINTS, typename stream_type, typename algorithm_type = DeviceThreadScheduler>
 struct BatchedAlignmentTraceback
 {
@@ -398,12 +418,12 @@ struct BatchedAlignmentTraceback
     void enact(stream_type stream, uint64 temp_size, uint8* temp, void* hip_stream = nullptr)
     {
         static_assert(sizeof(io::Cigar) == 2, "io::Cigar must be a uint16 bit-field");
-        const nvbio_hip_gotoh_scheme sc = priv::abi_scheme(stream.aligner().scheme);
         const nvbio_hip_string_set p = stream.m_patterns.abi(), t = stream.m_texts.abi();
-        hip_check(nvbio_hip_gotoh_traceback(&sc, int32(aligner_type::TYPE), &p, &t, stream.max_pattern_length(), stream.max_text_length(), stream.size(),
-                      stream.m_alignments.score, stream.m_alignments.sink, stream.m_alignments.source,
-                      reinterpret_cast<uint16*>(stream.m_cigars.cigar), stream.m_cigars.cigar_stride, stream.m_cigars.cigar_len,
-                      temp, temp_size, hip_stream), "nvbio_hip_gotoh_traceback");
+        priv::full_traceback(priv::abi_scheme(stream.aligner().scheme), int32(aligner_type::TYPE), p, t,
+                             stream.max_pattern_length(), stream.max_text_length(), stream.size(),
+                             stream.m_alignments.score, stream.m_alignments.sink, stream.m_alignments.source,
+                             reinterpret_cast<uint16*>(stream.m_cigars.cigar), stream.m_cigars.cigar_stride, stream.m_cigars.cigar_len,
+                             temp, temp_size, hip_stream);
     }
 };
 

@@ -1113,7 +1113,7 @@ struct traceback_runner
         const uint64 tb = band ? nvbio_hip_banded_gotoh_traceback_temp_bytes(band, maxP, n) : nvbio_hip_gotoh_traceback_temp_bytes(maxP, maxT, n);
         uint8* temp = m_temp.reserve(tb + 16u, hs);
         const int err = scheme.traceback(band, stream, t, ps, ts, quals, n_quals, source, cigar, stride, cigar_len, temp, tb, hs);
-        if (err == 801) { run_device(stream, hs, std::false_type()); return; }     // e.g. asymmetric linear gaps (scores run tuned, tracebacks do not), 8-bit patterns, values beyond int16
+        if (err == 801) { run_device(stream, hs, std::false_type()); return; }     // e.g. values beyond int16, 8-bit texts (asymmetric linear gaps and 8-bit patterns run tuned, scores and tracebacks alike)
         if (err != 0) fprintf(stderr, "compat traceback: err %d band %u n %u maxP %u maxT %u stride %u tb %llu quals %p n_quals %llu ps{words %p n %llu bits %u} ts{words %p n %llu}\n", err, band, n, maxP, maxT, stride,
                               (unsigned long long)tb, (const void*)quals, (unsigned long long)n_quals, (const void*)ps.words, (unsigned long long)ps.n_words, ps.bits, (const void*)ts.words, (unsigned long long)ts.n_words);
         check(err, "nvbio_hip_*_traceback");

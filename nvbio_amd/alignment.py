@@ -249,7 +249,9 @@ def batch_banded_alignment_score(band_len, aligner, patterns, texts, out_score=N
 class BatchedBandedAlignmentTraceback:
     """BatchedBandedAlignmentTraceback<BAND_LEN, CHECKPOINTS, stream, DeviceThreadScheduler> (batched.h:460-476)
     with nvBowtie's CIGAR-forming backtracer (alignment_utils.h:125-168).  CHECKPOINTS is accepted for
-    signature parity and ignored: the whole band's flow flags live in the temp storage."""
+    signature parity and ignored: the whole band's flow flags live in the temp storage.
+    Aligners: Gotoh (simple and quality-aware schemes), Smith-Waterman (deletion and insertion may differ) and edit
+    distance; patterns of 2, 4 or 8 bits, texts of 2 bits."""
 
     def __init__(self, band_len, checkpoints=32):
         if band_len not in (3, 5, 7, 15, 31):
@@ -320,8 +322,9 @@ def batch_banded_alignment_traceback(band_len, aligner, patterns, texts, max_pat
 
 
 def batch_alignment_traceback(aligner, patterns, texts, max_pattern_length=0, max_text_length=0, cigar_stride=64, quals=None, known_score=None):
-    """BatchedAlignmentTraceback<CHECKPOINTS, stream>::enact (batched.h:432-452) for the full-matrix Gotoh aligner with
-    nvBowtie's backtracer: returns dict(score, sink, source, cigar int16[n,stride], cigar_len) as the banded form does.
+    """BatchedAlignmentTraceback<CHECKPOINTS, stream>::enact (batched.h:432-452) for the full-matrix Gotoh, Smith-Waterman
+    (deletion and insertion may differ) and edit-distance aligners with nvBowtie's backtracer: returns dict(score, sink, source,
+    cigar int16[n,stride], cigar_len) as the banded form does.  Patterns of 2, 4 or 8 bits, texts of 2 bits.
     known_score (int32[n], Gotoh aligners): the caller knows every job's best score and that its alignment ends at the last text symbol
     (opposite-mate tracebacks); same results, the unreachable text rows are dropped first (nvbio_hip_gotoh_traceback*_known_score)."""
     n = len(patterns)

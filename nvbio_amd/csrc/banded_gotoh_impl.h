@@ -520,10 +520,6 @@ __device__ __forceinline__ uint4 fetch_quals16(const QualArgs& qa, uint64_t off)
 }
 __device__ __forceinline__ uint4 fetch_quals16(const NoQual&, uint64_t) { return make_uint4(0, 0, 0, 0); }
 
-__device__ __forceinline__ uint64_t fetch_pattern16(const Stream& s, uint64_t sym)
-{
-    return (s.bits == 4) ? fetch16_4bit(s, sym) : (s.bits == 8) ? fetch16_8bit(s, sym) : expand_2to4(fetch16_2bit(s, sym));
-}
 
 __host__ __device__ __forceinline__ uint32_t stage_words_pattern(uint32_t off, uint32_t M, uint32_t bits);
 

@@ -24,7 +24,8 @@ struct TracebackParams {
     StringSet       pat, txt;
     const uint8_t*  quals;          // nullable: quality byte of pattern symbol at stream index b + i
     uint64_t        n_quals;
-    int32_t         match, gap_open, gap_ext, txt_gap_open, txt_gap_ext;
+    int32_t         match, gap_open, gap_ext, txt_gap_open, txt_gap_ext;   // gap_*: the move from the previous row (F; `top` + deletion of the linear-gap aligners)
+    int32_t         row_gap_open, row_gap_ext;                             // the move along the row (E; `left` + insertion): == gap_* for the Gotoh schemes
     int32_t         mismatch[256];  // by quality byte (constant for SimpleGotohScheme)
     uint32_t        n;
     int32_t*        out_score;
@@ -38,6 +39,11 @@ struct TracebackParams {
     const uint32_t* pending;        // nullable: the jobs this launch works on (slot -> job), *pending_count of them
     const uint32_t* pending_count;
 };
+
+// 8-bit patterns come through the scorers' fold (fetch_pattern16 -> fetch16_8bit): bytes 0..3 stay, 255 becomes 15, any other byte 4; a
+// text position past the end then reads past_symbol() = 15, so that it equals byte 255 and nothing else.  For 2- and 4-bit patterns it
+// reads 255, which no nibble equals.
+__device__ __forceinline__ uint32_t past_symbol(const Stream& pat) { return pat.bits == 8 ? 15u : 255u; }
 
 template <uint32_t BAND>
 struct FlagRow {
@@ -72,8 +78,9 @@ __global__ __launch_bounds__(256) void banded_gotoh_traceback_kernel(const Trace
     if (N >= M)
     {
         // ---- forward pass: gotoh_banded_inl.h:434-640 with new_cell's flags kept ----
-        const int32_t G_o = p.gap_open, G_e = p.gap_ext;
-        const int32_t infimum = -32768 - max(max(G_o, G_e), max(p.txt_gap_open, p.txt_gap_ext));
+        const int32_t G_o = p.gap_open, G_e = p.gap_ext, E_o = p.row_gap_open, E_e = p.row_gap_ext;
+        const int32_t infimum = -32768 - max(max(max(G_o, G_e), max(E_o, E_e)), max(p.txt_gap_open, p.txt_gap_ext));
+        const uint32_t past = past_symbol(p.pat.s);
         uint32_t tc[BAND - 1];
         int32_t  H[BAND], F[BAND];
 #pragma unroll
@@ -91,7 +98,7 @@ __global__ __launch_bounds__(256) void banded_gotoh_traceback_kernel(const Trace
         for (uint32_t i = 0; i < M; ++i)
         {
             if ((i & 15u) == 0u) {
-                pq = (p.pat.s.bits == 2) ? expand_2to4(fetch16_2bit(p.pat.s, pb + i)) : fetch16_4bit(p.pat.s, pb + i);
+                pq = fetch_pattern16(p.pat.s, pb + i);
                 tg = expand_2to4(fetch16_2bit(p.txt.s, tb + i + BAND - 1));
             }
             const uint32_t q  = uint32_t(pq >> ((i & 15u) * 4u)) & 15u;
@@ -111,7 +118,7 @@ __global__ __launch_bounds__(256) void banded_gotoh_traceback_kernel(const Trace
                 H[0] = hi;
                 row.set(0, hdir | fdir);
             }
-            int32_t E = H[0] + G_o;
+            int32_t E = H[0] + E_o;
 #pragma unroll
             for (uint32_t j = 1; j < BAND - 1; ++j)
             {
@@ -126,11 +133,11 @@ __global__ __launch_bounds__(256) void banded_gotoh_traceback_kernel(const Trace
                 if (TYPE == NVBIO_HIP_LOCAL) { hi = max(hi, 0); if (hi == 0 && !p.no_sink) hdir = SINK; report(hi, i + j + 1, i + 1); }
                 H[j] = hi;
                 row.set(j, hdir | edir | fdir);
-                const int32_t eleft = E + G_e, ediagonal = hi + G_o;
+                const int32_t eleft = E + E_e, ediagonal = hi + E_o;
                 edir = eleft > ediagonal ? INSERTION_EXT : SUBSTITUTION;
                 E = max(ediagonal, eleft);
             }
-            const uint32_t g = (i + BAND - 1 < N) ? (uint32_t(tg >> ((i & 15u) * 4u)) & 15u) : 255u;
+            const uint32_t g = (i + BAND - 1 < N) ? (uint32_t(tg >> ((i & 15u) * 4u)) & 15u) : past;
             tc[BAND - 2] = QUIRK ? (g & 3u) : g;
             {
                 F[BAND - 1] = infimum;
@@ -228,6 +235,7 @@ __global__ __launch_bounds__(256) void banded_traceback_diagonal_kernel(const Tr
     const uint32_t M  = p.pat.length ? p.pat.length[tid] : p.pat.fixed_length;
     const uint32_t N  = p.txt.length ? p.txt.length[tid] : p.txt.fixed_length;
     const uint32_t by = sink.y, j = sink.x - sink.y;
+    const uint32_t past = past_symbol(p.pat.s);
     bool     found = false;
     uint32_t t = 0;
     if (!(TYPE == NVBIO_HIP_LOCAL && best <= 0))
@@ -242,7 +250,7 @@ __global__ __launch_bounds__(256) void banded_traceback_diagonal_kernel(const Tr
                 const uint32_t i = uint32_t(c0 + k), idx = i + j;
                 const uint32_t q = uint32_t(pq >> (4 * k)) & 15u;
                 uint32_t g = uint32_t(tg >> (4 * k)) & 15u;
-                if (!(idx + 2u <= band || idx < N)) g = (j == band - 1u) ? 255u : (quirk ? 3u : 255u);     // (the initial cache load is not range checked)
+                if (!(idx + 2u <= band || idx < N)) g = (j == band - 1u) ? past : (quirk ? 3u : past);     // (the initial cache load is not range checked)
                 int32_t sc = p.match;
                 if (g != q)
                 {
@@ -294,7 +302,7 @@ __global__ __launch_bounds__(256) void banded_traceback_diagonal_kernel(const Tr
         };
         // a group's rows c0 .. c0 + 15 (those below `by`) all compare against real text symbols
         auto inside = [&](const int32_t c0) { return uint32_t(min(c0 + 15, int32_t(by) - 1)) + j < N; };
-        auto load_p = [&](const int32_t c0) { return (p.pat.s.bits == 2) ? expand_2to4(fetch16_2bit(p.pat.s, pb + uint32_t(c0))) : fetch16_4bit(p.pat.s, pb + uint32_t(c0)); };
+        auto load_p = [&](const int32_t c0) { return fetch_pattern16(p.pat.s, pb + uint32_t(c0)); };
         auto load_t = [&](const int32_t c0) { return expand_2to4(fetch16_2bit(p.txt.s, tb + uint32_t(c0) + j)); };
         const uint4 no_q = make_uint4(0u, 0u, 0u, 0u);
         if (by <= 128u && p.pat.s.bits == 4u && !p.pat.s.lds && !p.txt.s.lds)
@@ -400,7 +408,7 @@ static int traceback_common(TracebackParams& p, int64_t A, int32_t type, uint32_
 {
     if (!patterns || !texts) return hipErrorInvalidValue;
     if (type < 0 || type > 2) return hipErrorInvalidValue;
-    if (!(patterns->bits == 2 || patterns->bits == 4) || texts->bits != 2) return hipErrorNotSupported;
+    if (!(patterns->bits == 2 || patterns->bits == 4 || patterns->bits == 8) || texts->bits != 2) return hipErrorNotSupported;
     if (!(band_len == 3 || band_len == 5 || band_len == 7 || band_len == 15 || band_len == 31)) return hipErrorNotSupported;
     if (n == 0) return hipSuccess;
     if (!out_score || !out_sink || !out_source || !out_cigar || !out_cigar_len || cigar_stride == 0) return hipErrorInvalidValue;
@@ -482,6 +490,7 @@ NVB_API int nvbio_hip_banded_gotoh_traceback(
     p.match = scheme->match;
     p.gap_open = scheme->gap_open; p.gap_ext = scheme->gap_ext;
     p.txt_gap_open = scheme->gap_open; p.txt_gap_ext = scheme->gap_ext;
+    p.row_gap_open = scheme->gap_open; p.row_gap_ext = scheme->gap_ext;
     for (int i = 0; i < 256; ++i) p.mismatch[i] = scheme->mismatch;
     const int64_t A = std::max(std::max(tb_abs(scheme->match), tb_abs(scheme->mismatch)), std::max(tb_abs(scheme->gap_open), tb_abs(scheme->gap_ext)));
     return traceback_common(p, A, type, band_len, patterns, texts, max_pattern_len, n, out_score, out_sink, out_source,
@@ -506,6 +515,7 @@ static int banded_traceback_qual(
     p.match = scheme->match;
     p.gap_open = scheme->pattern_gap_open; p.gap_ext = scheme->pattern_gap_ext;
     p.txt_gap_open = scheme->text_gap_open; p.txt_gap_ext = scheme->text_gap_ext;
+    p.row_gap_open = scheme->pattern_gap_open; p.row_gap_ext = scheme->pattern_gap_ext;
     int64_t A = std::max(std::max(tb_abs(scheme->match), tb_abs(scheme->pattern_gap_open)), std::max(tb_abs(scheme->pattern_gap_ext),
                 std::max(tb_abs(scheme->text_gap_open), tb_abs(scheme->text_gap_ext))));
     for (int i = 0; i < 256; ++i) { p.mismatch[i] = scheme->mismatch[i]; A = std::max(A, tb_abs(scheme->mismatch[i])); }
@@ -513,9 +523,10 @@ static int banded_traceback_qual(
                             out_cigar, cigar_stride, out_cigar_len, temp, temp_bytes, to_stream(stream), known ? score_prefilled : score_qual, scheme);
 }
 
-// SmithWatermanAligner / EditDistanceAligner in the band (sw_banded_inl.h:405-470, 748-800): with deletion == insertion the
-// directions are those of the Gotoh recurrence with gap_open == gap_ext; the reference's banded SW context does not mark
-// zero cells as SINK, so a LOCAL walk runs to the first pattern row -- kept.
+// SmithWatermanAligner / EditDistanceAligner in the band (sw_banded_inl.h:405-470, 748-800): the directions are those of the Gotoh
+// recurrence with gap open == gap extension in each direction -- `deletion` for the move from the previous row (and for GLOBAL's row
+// zero, j * deletion), `insertion` for the move along the row.  H >= F and H >= E in every cell then, so the extension flags never
+// fire.  The reference's banded SW context does not mark zero cells as SINK, so a LOCAL walk runs to the first pattern row -- kept.
 NVB_API int nvbio_hip_banded_sw_traceback(
     const nvbio_hip_sw_scheme* scheme, int32_t type, uint32_t band_len,
     const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts,
@@ -527,13 +538,13 @@ NVB_API int nvbio_hip_banded_sw_traceback(
     (void)max_text_len;
     using namespace nvb;
     if (!scheme) return hipErrorInvalidValue;
-    if (scheme->deletion != scheme->insertion) return hipErrorNotSupported;
     TracebackParams p;
     p.quals = nullptr; p.n_quals = 0; p.no_sink = 1;
     p.match = scheme->match;
     p.gap_open = p.gap_ext = p.txt_gap_open = p.txt_gap_ext = scheme->deletion;
+    p.row_gap_open = p.row_gap_ext = scheme->insertion;
     for (int i = 0; i < 256; ++i) p.mismatch[i] = scheme->mismatch;
-    const int64_t A = std::max(std::max(tb_abs(scheme->match), tb_abs(scheme->mismatch)), tb_abs(scheme->deletion));
+    const int64_t A = std::max(std::max(tb_abs(scheme->match), tb_abs(scheme->mismatch)), std::max(tb_abs(scheme->deletion), tb_abs(scheme->insertion)));
     return traceback_common(p, A, type, band_len, patterns, texts, max_pattern_len, n, out_score, out_sink, out_source,
                             out_cigar, cigar_stride, out_cigar_len, temp, temp_bytes, to_stream(stream));
 }

@@ -193,6 +193,11 @@ __device__ __forceinline__ uint64_t expand_2to4(uint32_t v)
     x = (x | (x <<  2)) & 0x3333333333333333ull;
     return x;
 }
+// 16 pattern symbols as nibbles, whatever the stream's width (an 8-bit stream through the fold above)
+__device__ __forceinline__ uint64_t fetch_pattern16(const Stream& s, uint64_t sym)
+{
+    return (s.bits == 4) ? fetch16_4bit(s, sym) : (s.bits == 8) ? fetch16_8bit(s, sym) : expand_2to4(fetch16_2bit(s, sym));
+}
 // one symbol (generic, used off the hot loops)
 __device__ __forceinline__ uint32_t get_symbol(const Stream& s, uint64_t sym)
 {

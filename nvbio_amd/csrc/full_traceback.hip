@@ -23,7 +23,8 @@ enum : uint32_t { T_SUBSTITUTION = 0, T_INSERTION = 1, T_DELETION = 2, T_SINK = 
 
 struct FullTbParams {
     StringSet pat, txt;
-    int32_t   match, mismatch, gap_open, gap_ext;
+    int32_t   match, mismatch, gap_open, gap_ext;    // gap_*: the move along the text (F; `top` + deletion of the linear-gap aligners)
+    int32_t   pat_gap_open, pat_gap_ext;             // the move down the pattern (E; `left` + insertion) and the row before the text: == gap_* for the Gotoh schemes
     uint32_t  n, max_text_len;
     int32_t*  out_score; uint2* out_sink; uint2* out_source;
     uint16_t* out_cigar; uint32_t cigar_stride; uint32_t* out_cigar_len;
@@ -72,8 +73,8 @@ __global__ void __launch_bounds__(256) full_gotoh_traceback_kernel(const FullTbP
     uint32_t bx = 0xFFFFFFFFu, by = 0xFFFFFFFFu;
     auto report = [&](const int32_t s, const uint32_t x, const uint32_t y) { if (best <= s) { best = s; bx = x; by = y; } };
 
-    const int32_t G_o = p.gap_open, G_e = p.gap_ext;
-    const int32_t infimum = -32768 - min(G_o, G_e);
+    const int32_t G_o = p.gap_open, G_e = p.gap_ext, E_o = p.pat_gap_open, E_e = p.pat_gap_ext;
+    const int32_t infimum = -32768 - min(min(G_o, G_e), min(E_o, E_e));
     const uint32_t n_blocks = max(1u, (M + BL - 1u) / BL);
     int32_t H_band[BL + 1], F_band[BL + 1];
     uint32_t q_cache[BL];
@@ -93,7 +94,7 @@ __global__ void __launch_bounds__(256) full_gotoh_traceback_kernel(const FullTbP
         }
         #pragma unroll
         for (uint32_t j = 0; j <= BL; ++j) {
-            H_band[j] = (TYPE != NVBIO_HIP_LOCAL) ? (block + j > 0u ? G_o + G_e * int32_t(block + j - 1u) : 0) : 0;
+            H_band[j] = (TYPE != NVBIO_HIP_LOCAL) ? (block + j > 0u ? E_o + E_e * int32_t(block + j - 1u) : 0) : 0;
             F_band[j] = infimum;
         }
         int32_t temp_i = H_band[0];
@@ -119,7 +120,7 @@ __global__ void __launch_bounds__(256) full_gotoh_traceback_kernel(const FullTbP
                 const int32_t ftop = F_band[j] + G_e, htop = H_band[j] + G_o;
                 F_band[j] = max(ftop, htop);
                 const uint32_t fdir = ftop > htop ? T_DELETION_EXT : T_SUBSTITUTION;
-                const int32_t eleft = E + G_e, hleft = H_band[j - 1] + G_o;
+                const int32_t eleft = E + E_e, hleft = H_band[j - 1] + E_o;
                 E = max(eleft, hleft);
                 const uint32_t edir = eleft > hleft ? T_INSERTION_EXT : T_SUBSTITUTION;
                 const int32_t diagonal = H_diag + (r_i == q_cache[j - 1] ? p.match : x_cache[j - 1]);
@@ -244,8 +245,8 @@ __global__ void __launch_bounds__(256) full_gotoh_traceback_wave_kernel(const Fu
     uint32_t bx = 0xFFFFFFFFu, by = 0xFFFFFFFFu;
     auto report = [&](const int32_t s, const uint32_t x, const uint32_t y) { if (best <= s) { best = s; bx = x; by = y; } };
 
-    const int32_t G_o = p.gap_open, G_e = p.gap_ext;
-    const int32_t infimum = -32768 - min(G_o, G_e);
+    const int32_t G_o = p.gap_open, G_e = p.gap_ext, E_o = p.pat_gap_open, E_e = p.pat_gap_ext;
+    const int32_t infimum = -32768 - min(min(G_o, G_e), min(E_o, E_e));
     int32_t  H_band[BL + 1], F_band[BL + 1];
     uint32_t q_cache[BL];
     int32_t  x_cache[BL];
@@ -259,7 +260,7 @@ __global__ void __launch_bounds__(256) full_gotoh_traceback_wave_kernel(const Fu
     }
     #pragma unroll
     for (uint32_t j = 0; j <= BL; ++j) {
-        H_band[j] = (TYPE != NVBIO_HIP_LOCAL) ? (block + j > 0u ? G_o + G_e * int32_t(block + j - 1u) : 0) : 0;
+        H_band[j] = (TYPE != NVBIO_HIP_LOCAL) ? (block + j > 0u ? E_o + E_e * int32_t(block + j - 1u) : 0) : 0;
         F_band[j] = infimum;
     }
     int32_t temp_i = H_band[0];
@@ -300,7 +301,7 @@ __global__ void __launch_bounds__(256) full_gotoh_traceback_wave_kernel(const Fu
             const int32_t ftop = F_band[j] + G_e, htop = H_band[j] + G_o;
             F_band[j] = max(ftop, htop);
             const uint32_t fdir = ftop > htop ? T_DELETION_EXT : T_SUBSTITUTION;
-            const int32_t eleft = E + G_e, hleft = H_band[j - 1] + G_o;
+            const int32_t eleft = E + E_e, hleft = H_band[j - 1] + E_o;
             E = max(eleft, hleft);
             const uint32_t edir = eleft > hleft ? T_INSERTION_EXT : T_SUBSTITUTION;
             const int32_t diagonal = H_diag + (r_i == q_cache[j - 1] ? p.match : x_cache[j - 1]);
@@ -421,7 +422,8 @@ __global__ void __launch_bounds__(256) full_traceback_diagonal_kernel(const Full
         {
             const uint32_t cnt = min(16u, kmax - k0);
             const uint32_t lo_p = by - k0 - cnt, lo_t = bx - k0 - cnt;                 // lowest symbol index of this group
-            const uint64_t pq = (p.pat.s.bits == 2) ? expand_2to4(fetch16_2bit(p.pat.s, pb + lo_p)) : fetch16_4bit(p.pat.s, pb + lo_p);
+            // (8-bit patterns through the scorers' fold, fetch16_8bit: a byte no 2-bit text symbol equals becomes 4 or 15)
+            const uint64_t pq = fetch_pattern16(p.pat.s, pb + lo_p);
             const uint64_t tg = expand_2to4(fetch16_2bit(p.txt.s, tb + lo_t));
             for (uint32_t u = 0; u < cnt; ++u)
             {
@@ -537,18 +539,31 @@ NVB_API uint64_t nvbio_hip_gotoh_traceback_temp_bytes(uint32_t max_pattern_len, 
 static std::atomic<uint64_t> g_known_score_redone{0};
 
 struct TbQualPart { const uint8_t* quals; uint64_t n_quals; const int32_t* mismatch; int32_t text_gap_open, text_gap_ext; };
+// what one call traces with: the Gotoh costs (for SW / ED gap_open == gap_ext == `deletion`, paid along the text), the quality part of
+// nvBowtie's scheme or nullptr, and for SW / ED the linear cost of the move down the pattern (sw_inl.h:475-500: top + deletion, left +
+// insertion; the row before the text is insertion * j, the column before the pattern deletion * (i + 1))
+struct TbScheme {
+    nvbio_hip_gotoh_scheme gotoh;
+    const TbQualPart*      qual;
+    bool                   linear;
+    int32_t                insertion;
+    int32_t pat_gap_open() const { return linear ? insertion : gotoh.gap_open; }
+    int32_t pat_gap_ext()  const { return linear ? insertion : gotoh.gap_ext; }
+};
 
 static int full_traceback_core(
-    const nvbio_hip_gotoh_scheme* scheme, const TbQualPart* qual, int32_t type, uint32_t block_len,
+    const TbScheme& tbs, int32_t type, uint32_t block_len,
     const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts,
     uint32_t max_pattern_len, uint32_t max_text_len, uint32_t n,
     int32_t* out_score, uint32_t* out_sink, uint32_t* out_source,
     uint16_t* out_cigar, uint32_t cigar_stride, uint32_t* out_cigar_len,
     void* temp, uint64_t temp_bytes, void* stream, const int32_t* known_score = nullptr)
 {
-    if (!scheme || !patterns || !texts) return hipErrorInvalidValue;
+    const nvbio_hip_gotoh_scheme* scheme = &tbs.gotoh;
+    const TbQualPart* qual = tbs.qual;
+    if (!patterns || !texts) return hipErrorInvalidValue;
     if (type < 0 || type > 2) return hipErrorInvalidValue;
-    if (!(patterns->bits == 2 || patterns->bits == 4) || texts->bits != 2) return hipErrorNotSupported;
+    if (!(patterns->bits == 2 || patterns->bits == 4 || patterns->bits == 8) || texts->bits != 2) return hipErrorNotSupported;
     if (n == 0) return hipSuccess;
     if (!out_score || !out_sink || !out_source || !out_cigar || !out_cigar_len || cigar_stride == 0) return hipErrorInvalidValue;
     if (!patterns->words || !texts->words || !patterns->begin || !texts->begin || patterns->n_words == 0 || texts->n_words == 0) return hipErrorInvalidValue;
@@ -559,8 +574,9 @@ static int full_traceback_core(
     auto iabs = [](int32_t v) { return v < 0 ? -int64_t(v) : int64_t(v); };
     int64_t A = std::max(std::max(iabs(scheme->match), iabs(scheme->mismatch)), std::max(iabs(scheme->gap_open), iabs(scheme->gap_ext)));
     if (qual) { for (int i = 0; i < 256; ++i) A = std::max(A, iabs(qual->mismatch[i])); A = std::max(A, std::max(iabs(qual->text_gap_open), iabs(qual->text_gap_ext))); }
+    if (tbs.linear) A = std::max(A, iabs(tbs.insertion));
     const int64_t span = (type == NVBIO_HIP_GLOBAL) ? int64_t(maxM) + maxN + 4 : int64_t(maxM) + 4;
-    const bool gaps_cost = scheme->gap_open <= 0 && scheme->gap_ext <= 0 && (!qual || (qual->text_gap_open <= 0 && qual->text_gap_ext <= 0));
+    const bool gaps_cost = scheme->gap_open <= 0 && scheme->gap_ext <= 0 && (!qual || (qual->text_gap_open <= 0 && qual->text_gap_ext <= 0)) && (!tbs.linear || tbs.insertion <= 0);
     if (!(gaps_cost && span * A < 30000)) return hipErrorNotSupported;   // int16 checkpoints / columns exact only here (no gap move may earn score)
     const uint64_t need = nvbio_hip_gotoh_traceback_temp_bytes(maxM, maxN, n);
     if (!temp || temp_bytes < need) return hipErrorInvalidValue;
@@ -568,6 +584,7 @@ static int full_traceback_core(
     FullTbParams p;
     p.pat = make_string_set(patterns); p.txt = make_string_set(texts);
     p.match = scheme->match; p.mismatch = scheme->mismatch; p.gap_open = scheme->gap_open; p.gap_ext = scheme->gap_ext;
+    p.pat_gap_open = tbs.pat_gap_open(); p.pat_gap_ext = tbs.pat_gap_ext();
     p.n = n; p.max_text_len = maxN;
     p.quals = qual ? qual->quals : nullptr; p.n_quals = qual ? qual->n_quals : 0;
     for (int i = 0; i < 256; ++i) p.mm_lut[i] = qual ? qual->mismatch[i] : scheme->mismatch;
@@ -577,6 +594,7 @@ static int full_traceback_core(
     p.column = static_cast<uint32_t*>(temp);
     p.flags  = p.column + uint64_t(maxN) * n;
     p.pending = nullptr; p.pending_count = nullptr;
+    // (cropping is for queued and _known_score jobs, which are Gotoh's: SW / ED take neither route, so `insertion` has no part in it)
     p.crop_open = int32_t(std::min(iabs(scheme->gap_open), qual ? iabs(qual->text_gap_open) : iabs(scheme->gap_open)));
     p.crop_ext  = int32_t(std::min(iabs(scheme->gap_ext),  qual ? iabs(qual->text_gap_ext)  : iabs(scheme->gap_ext)));
     const dim3 grid((n + 255u) / 256u), block(256);
@@ -698,7 +716,7 @@ static int full_traceback_core(
     hipLaunchKernelGGL(gather_jobs_kernel, mgrid, block, 0, s, m, bad, make_string_set(patterns), make_string_set(whole_texts), pb, pl, tb, tl);
     nvbio_hip_string_set sp = *patterns, st = *whole_texts;
     sp.begin = pb; sp.length = pl; sp.fixed_length = 0; st.begin = tb; st.length = tl; st.fixed_length = 0;
-    int e2 = full_traceback_core(scheme, qual, type, block_len, &sp, &st, maxM, maxN, m, r_score, reinterpret_cast<uint32_t*>(r_sink), reinterpret_cast<uint32_t*>(r_src),
+    int e2 = full_traceback_core(tbs, type, block_len, &sp, &st, maxM, maxN, m, r_score, reinterpret_cast<uint32_t*>(r_sink), reinterpret_cast<uint32_t*>(r_src),
                                  r_cigar, cigar_stride, r_len, blk, sub_temp, stream);
     if (e2 == hipSuccess) {
         hipLaunchKernelGGL(scatter_tracebacks_kernel, dim3(m), block, 0, s, m, bad, r_score, r_sink, r_src, r_cigar, r_len, cigar_stride,
@@ -721,13 +739,15 @@ NVB_API int nvbio_hip_gotoh_traceback(
     uint16_t* out_cigar, uint32_t cigar_stride, uint32_t* out_cigar_len,
     void* temp, uint64_t temp_bytes, void* stream)
 {
-    return full_traceback_core(scheme, nullptr, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
+    if (!scheme) return hipErrorInvalidValue;
+    const TbScheme tbs = { *scheme, nullptr, false, 0 };
+    return full_traceback_core(tbs, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
                                out_cigar, cigar_stride, out_cigar_len, temp, temp_bytes, stream);
 }
 
-// SmithWatermanAligner / EditDistanceAligner (sw_inl.h:389-396, 475-500, 1660-1700): with deletion == insertion the matrix, the
-// flow directions and the walk are those of Gotoh with gap_open == gap_ext (the extension flags never fire); the sink comes
-// from the 16-column pattern-blocking score pass.
+// SmithWatermanAligner / EditDistanceAligner (sw_inl.h:389-396, 475-500, 1660-1700): the matrix, the flow directions and the walk
+// are those of Gotoh with gap open == gap extension in each direction (the extension flags never fire) -- `deletion` along the text,
+// `insertion` down the pattern, the other way round than in the band; the sink comes from the 16-column pattern-blocking score pass.
 NVB_API int nvbio_hip_sw_traceback(
     const nvbio_hip_sw_scheme* scheme, int32_t type,
     const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts,
@@ -737,9 +757,8 @@ NVB_API int nvbio_hip_sw_traceback(
     void* temp, uint64_t temp_bytes, void* stream)
 {
     if (!scheme) return hipErrorInvalidValue;
-    if (scheme->deletion != scheme->insertion) return hipErrorNotSupported;
-    const nvbio_hip_gotoh_scheme g = { scheme->match, scheme->mismatch, scheme->deletion, scheme->deletion };
-    return full_traceback_core(&g, nullptr, type, 16u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
+    const TbScheme tbs = { { scheme->match, scheme->mismatch, scheme->deletion, scheme->deletion }, nullptr, true, scheme->insertion };
+    return full_traceback_core(tbs, type, 16u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
                                out_cigar, cigar_stride, out_cigar_len, temp, temp_bytes, stream);
 }
 
@@ -756,9 +775,9 @@ NVB_API int nvbio_hip_gotoh_traceback_qual(
     if (n != 0 && (!quals || n_quals == 0)) return hipErrorInvalidValue;
     int32_t worst = 0;
     for (int i = 0; i < 256; ++i) worst = std::min(worst, scheme->mismatch[i]);
-    const nvbio_hip_gotoh_scheme g = { scheme->match, worst, scheme->pattern_gap_open, scheme->pattern_gap_ext };
     const TbQualPart q = { quals, n_quals, scheme->mismatch, scheme->text_gap_open, scheme->text_gap_ext };
-    return full_traceback_core(&g, &q, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
+    const TbScheme tbs = { { scheme->match, worst, scheme->pattern_gap_open, scheme->pattern_gap_ext }, &q, false, 0 };
+    return full_traceback_core(tbs, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
                                out_cigar, cigar_stride, out_cigar_len, temp, temp_bytes, stream);
 }
 
@@ -773,8 +792,9 @@ NVB_API int nvbio_hip_gotoh_traceback_known_score(
     uint16_t* out_cigar, uint32_t cigar_stride, uint32_t* out_cigar_len,
     void* temp, uint64_t temp_bytes, void* stream)
 {
-    if (n != 0 && !known_score) return hipErrorInvalidValue;
-    return full_traceback_core(scheme, nullptr, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
+    if (!scheme || (n != 0 && !known_score)) return hipErrorInvalidValue;
+    const TbScheme tbs = { *scheme, nullptr, false, 0 };
+    return full_traceback_core(tbs, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
                                out_cigar, cigar_stride, out_cigar_len, temp, temp_bytes, stream, known_score);
 }
 
@@ -790,8 +810,8 @@ NVB_API int nvbio_hip_gotoh_traceback_qual_known_score(
     if (n != 0 && (!quals || n_quals == 0 || !known_score)) return hipErrorInvalidValue;
     int32_t worst = 0;
     for (int i = 0; i < 256; ++i) worst = std::min(worst, scheme->mismatch[i]);
-    const nvbio_hip_gotoh_scheme g = { scheme->match, worst, scheme->pattern_gap_open, scheme->pattern_gap_ext };
     const TbQualPart q = { quals, n_quals, scheme->mismatch, scheme->text_gap_open, scheme->text_gap_ext };
-    return full_traceback_core(&g, &q, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
+    const TbScheme tbs = { { scheme->match, worst, scheme->pattern_gap_open, scheme->pattern_gap_ext }, &q, false, 0 };
+    return full_traceback_core(tbs, type, 8u, patterns, texts, max_pattern_len, max_text_len, n, out_score, out_sink, out_source,
                                out_cigar, cigar_stride, out_cigar_len, temp, temp_bytes, stream, known_score);
 }
