@@ -364,6 +364,48 @@ int nvbio_hip_alignment_score_qual_jobs(
     uint32_t n, const uint32_t* n_on_device, const uint32_t* job_index, const uint32_t* gate, uint32_t gate_limit, int32_t wave_form,
     int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok /* nullable */, void* stream);
 
+/* Ungapped ("Hamming") scoring: BatchedAlignmentScore<stream,...>::enact for HammingDistanceAligner<TYPE, scheme, PatternBlockingTag>
+ * (hamming/hamming_inl.h:413-720) -- the aligner nvBowtie scores the opposite mate with under --ungapped-mates (score_paired.cu:110-137).
+ *   H(i,j) = H(i-1,j-1) + (text[i] == pattern[j] ? match : mismatch[q_j]),   clamped at 0 after every cell for LOCAL,
+ * and EVERY border is zero, for all three types: the sum runs along the diagonal back to the top row or the left column, whichever
+ * comes first, so a pattern may hang over the text's start and the part before it is free.  A pattern symbol that equals no text
+ * symbol (codes >= 4) mismatches.  Reports go to a fresh BestSink (of equal scores the one reported last stays):
+ *   LOCAL        every cell, by 16-column pattern block, then text row i, then column j inside the block; sink (i+1, j)
+ *   SEMI_GLOBAL  H(i, M) for i = 0..N-1; sink (i+1, M)
+ *   GLOBAL       H(N-1, M) alone, sink (N, M); an empty text reports the zero border.
+ * Early exit: after every 16-column block except the last the job stops with out_ok = 0 when
+ *   max_i H(i, block end) + (M - block end) * match < min_score[job]            (min_score == NULL: -(1<<30) for every job, which
+ *                                                                                only an empty text's edge, INT32_MIN, falls below)
+ * and its sink keeps what it had seen (nothing, for SEMI_GLOBAL and GLOBAL: score = -(1<<30), sink = (0xFFFFFFFF,0xFFFFFFFF)).
+ * This test is NOT a bound: diagonals that enter a later block from the top border start at 0 there, so jobs whose final best does
+ * meet min_score are declined too (M = 17, N = 1).  It is reproduced as it is -- nvBowtie's records depend on it.  Values are kept in
+ * 32 bits; between blocks they pass through the reference's int16 column, which is modelled (the low 16 bits, sign-extended).
+ * Every job writes its three outputs.  Limits (801 beyond them): texts 2-bit, patterns 2-, 4- or 8-bit; algorithm =
+ * NVBIO_HIP_PATTERN_BLOCKING only; max_pattern_len <= 4096; |match|, |mismatch| <= 2^20; max_text_len as far as one job's working
+ * set (2.25 bytes per text symbol + 4.5 per pattern symbol + 1 KB) fits the 160 KB of LDS a workgroup may have (65535 with
+ * 1024-symbol patterns does: 152 KB).  The simple scheme reads `match` and `mismatch` only. */
+int nvbio_hip_hamming_score(
+    const nvbio_hip_sw_scheme* scheme /* host */, int32_t algorithm, int32_t type,
+    const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts,
+    uint32_t max_pattern_len, uint32_t max_text_len, const int32_t* min_score /* device, nullable */,
+    uint32_t n, int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok /* nullable */, void* stream);
+/* ... with nvBowtie's quality scheme: mismatch[quals[b + j]] for symbol j of the pattern that begins at stream index b (as in
+ * nvbio_hip_banded_gotoh_score_qual); the gap fields are not read */
+int nvbio_hip_hamming_score_qual(
+    const nvbio_hip_gotoh_qual_scheme* scheme /* host */, int32_t algorithm, int32_t type,
+    const nvbio_hip_string_set* patterns, const uint8_t* quals, uint64_t n_quals, const nvbio_hip_string_set* texts,
+    uint32_t max_pattern_len, uint32_t max_text_len, const int32_t* min_score /* device, nullable */,
+    uint32_t n, int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok /* nullable */, void* stream);
+/* ... with the job control of nvbio_hip_alignment_score_qual_jobs (the kernel is the same one wave per job in both forms):
+ * wave_form = 0 runs jobs [0, n) when *gate > gate_limit (gate == NULL: always); wave_form = 1 runs entries [0, *n_on_device) of
+ * job_index, each in place, when *gate <= gate_limit.  n bounds the launch; the host never reads a device-side count. */
+int nvbio_hip_hamming_score_qual_jobs(
+    const nvbio_hip_gotoh_qual_scheme* scheme /* host */, int32_t algorithm, int32_t type,
+    const nvbio_hip_string_set* patterns, const uint8_t* quals, uint64_t n_quals, const nvbio_hip_string_set* texts,
+    uint32_t max_pattern_len, uint32_t max_text_len, const int32_t* min_score /* device, nullable */,
+    uint32_t n, const uint32_t* n_on_device, const uint32_t* job_index, const uint32_t* gate, uint32_t gate_limit, int32_t wave_form,
+    int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok /* nullable */, void* stream);
+
 /* nvbio::fm_index<rank_dictionary<2,64,PackedStream<.,uint8,2,true>,.,.>, SSA_index_multiple_context<SA_INT>, const uint32*>
  * (nvbio/fmindex/fmindex.h:341-387) in the production interleaved layout
  * (nvbio/io/fmindex/fmindex.h:159-174, fmindex_impl.cu:305-327):
@@ -457,6 +499,14 @@ int nvbio_hip_banded_sw_score_host(const nvbio_hip_sw_scheme* scheme, int32_t ty
 int nvbio_hip_alignment_score_host(int32_t aligner, int32_t algorithm, const int32_t* scheme4, int32_t type,
                                    const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts, const int32_t* min_score /* nullable */,
                                    uint32_t n, int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok /* nullable */, int32_t n_threads);
+/* nvbio_hip_hamming_score / _qual: both algorithm tags, no shape limits (TextBlockingTag never exits early) */
+int nvbio_hip_hamming_score_host(const nvbio_hip_sw_scheme* scheme, int32_t algorithm, int32_t type,
+                                 const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts, const int32_t* min_score /* nullable */,
+                                 uint32_t n, int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok /* nullable */, int32_t n_threads);
+int nvbio_hip_hamming_score_qual_host(const nvbio_hip_gotoh_qual_scheme* scheme, int32_t algorithm, int32_t type,
+                                      const nvbio_hip_string_set* patterns, const uint8_t* quals, uint64_t n_quals, const nvbio_hip_string_set* texts,
+                                      const int32_t* min_score /* nullable */,
+                                      uint32_t n, int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok /* nullable */, int32_t n_threads);
 int nvbio_hip_fm_rank_host(const nvbio_hip_fmindex* fmi, const uint32_t* k, const uint8_t* c, uint32_t n, uint32_t* out, int32_t n_threads);
 int nvbio_hip_fm_match_host(const nvbio_hip_fmindex* fmi, const nvbio_hip_string_set* seeds, uint32_t n, uint32_t* out_range, int32_t n_threads);
 int nvbio_hip_fm_locate_host(const nvbio_hip_fmindex* fmi, const uint32_t* sa_rows, uint32_t n, uint32_t* out_pos, int32_t n_threads);

@@ -28,7 +28,7 @@ enum ScoringMode       { EditDistanceMode = 0, SmithWatermanMode = 1 };         
 struct Params : public ParamsPOD
 {
     Params() : max_dist(15), alignment_type(EndToEndAlignment), no_multi_hits(false), fw(true), rc(true), hits_stride(0), finish_alignments(true),
-               scoring_mode(SmithWatermanMode) {}
+               scoring_mode(SmithWatermanMode), ungapped_mates(false) {}
     SelectParamsPOD select;
     uint32 max_dist; AlignmentTypeMode alignment_type; bool no_multi_hits, fw, rc; uint32 hits_stride;
     bool   finish_alignments;      ///< run finish_alignment_best (MD strings, edit distances, final scores) as the reference always does
@@ -36,6 +36,11 @@ struct Params : public ParamsPOD
     /// edit-distance aligner against score-min = -max_dist (params.cpp:203-204); MAPQ and the final scores of finish_alignment still come
     /// from the Smith-Waterman scheme the caller passes (aligner_best_approx.h:294-296, traceback.cu:146-160), as in the reference
     ScoringMode scoring_mode;
+    /// --ungapped-mates (params.cpp:136, score_paired.cu:110-137; best_approx_paired only): in Smith-Waterman mode the opposite mate is
+    /// scored by the ungapped aligner (HammingDistanceAligner over the same scheme, scoring.h:214-215: nvbio_hip_hamming_score_qual) in a
+    /// window sized for zero text gaps (max_text_gaps of that aligner is 0); memo, finish, reduce and the -- gapped -- traceback are as
+    /// without it.  In edit-distance mode the "ungapped" aligners are the edit-distance ones (scoring.h:142-143): the flag changes nothing.
+    bool ungapped_mates;
     /// the search scheme and thresholds of the mode
     aln::SmithWatermanScoringScheme search_scheme(const aln::SmithWatermanScoringScheme& sw) const { return scoring_mode == EditDistanceMode ? aln::SmithWatermanScoringScheme::edit_distance() : sw; }
     ScoreLimits search_limits(const ScoreLimits& sw) const { return scoring_mode == EditDistanceMode ? ScoreLimits(0, SimpleFunc(SimpleFunc::LinearFunc, -float(max_dist), 0.0f)) : sw; }
@@ -644,8 +649,15 @@ private:
 
                     // opposite_score_best over the hits whose anchor scored: every hit gets a job, the invalid ones an empty text
                     stats.clock.begin("opposite_score", hip_stream);
+                    // (ungapped mates: the window formula counts the text gaps a threshold affords by opening one and extending it while the score
+                    // holds, utils_inl.h:181-204; an opening that costs nothing and an extension that no threshold affords count to zero, which is
+                    // max_text_gaps of the ungapped aligner)
+                    const bool  ungapped = params.ungapped_mates && !ed_mode;
+                    const int32 UNGAPPED_TEXT_GAP_EXT = -(1 << 29);
+                    const auto  full_score_jobs = ungapped ? nvbio_hip_hamming_score_qual_jobs : nvbio_hip_alignment_score_qual_jobs;
+                    const auto  full_score      = ungapped ? nvbio_hip_hamming_score_qual : nvbio_hip_alignment_score_qual;
                     hip_check(nvbio_hip_opposite_score_setup(nh, queues.hit_read_id.data(), hit_seed, queues.hit_loc.data(), hit_score.data(), worst_score, a_reads.read_len, o_reads.read_len, a_reads.fixed(), o_reads.fixed(),
-                                                             best, best_o, BATCH_SIZE, sc.match, min_score_table.data(), sc.text_gap_open, sc.text_gap_ext, &app,
+                                                             best, best_o, BATCH_SIZE, sc.match, min_score_table.data(), ungapped ? 0 : sc.text_gap_open, ungapped ? UNGAPPED_TEXT_GAP_EXT : sc.text_gap_ext, &app,
                                                              o_valid.data(), min_score.data(), o_rc.data(), o_gbegin.data(), o_gend.data(),
                                                              o_reads.read_begin, o_reads.rc_offset, pat_begin.data(), txt_begin.data(), txt_len.data(), hip_stream), "nvbio_hip_opposite_score_setup");
                     if (o_reads.read_len)           // mates of their own lengths: each job's pattern length is its read's
@@ -664,16 +676,16 @@ private:
                         if (wave_up_to)
                         {
                             hip_check(nvbio_hip_list_flagged(nh, o_valid.data(), 1u, a_live_count.data(), a_live_idx.data(), hip_stream), "nvbio_hip_list_flagged");
-                            hip_check(nvbio_hip_alignment_score_qual_jobs(&sc, NVBIO_HIP_PATTERN_BLOCKING, int32(TYPE), &p, o_reads.quals, o_reads.n_quals, &t, L, pe.max_frag_len + L,
+                            hip_check(full_score_jobs(&sc, NVBIO_HIP_PATTERN_BLOCKING, int32(TYPE), &p, o_reads.quals, o_reads.n_quals, &t, L, pe.max_frag_len + L,
                                                                           min_score.data(), nh, nullptr, nullptr, a_live_count.data(), wave_up_to, 0, raw_score.data(), sinks.data(), nullptr,
-                                                                          hip_stream), "nvbio_hip_alignment_score_qual_jobs");
-                            hip_check(nvbio_hip_alignment_score_qual_jobs(&sc, NVBIO_HIP_PATTERN_BLOCKING, int32(TYPE), &p, o_reads.quals, o_reads.n_quals, &t, L, pe.max_frag_len + L,
+                                                                          hip_stream), ungapped ? "nvbio_hip_hamming_score_qual_jobs" : "nvbio_hip_alignment_score_qual_jobs");
+                            hip_check(full_score_jobs(&sc, NVBIO_HIP_PATTERN_BLOCKING, int32(TYPE), &p, o_reads.quals, o_reads.n_quals, &t, L, pe.max_frag_len + L,
                                                                           min_score.data(), std::min(nh, wave_up_to), a_live_count.data(), a_live_idx.data(), a_live_count.data(), wave_up_to, 1,
-                                                                          raw_score.data(), sinks.data(), nullptr, hip_stream), "nvbio_hip_alignment_score_qual_jobs");
+                                                                          raw_score.data(), sinks.data(), nullptr, hip_stream), ungapped ? "nvbio_hip_hamming_score_qual_jobs" : "nvbio_hip_alignment_score_qual_jobs");
                         }
                         else
-                            hip_check(nvbio_hip_alignment_score_qual(&sc, NVBIO_HIP_PATTERN_BLOCKING, int32(TYPE), &p, o_reads.quals, o_reads.n_quals, &t, L, pe.max_frag_len + L,
-                                                                     min_score.data(), nh, raw_score.data(), sinks.data(), nullptr, hip_stream), "nvbio_hip_alignment_score_qual");
+                            hip_check(full_score(&sc, NVBIO_HIP_PATTERN_BLOCKING, int32(TYPE), &p, o_reads.quals, o_reads.n_quals, &t, L, pe.max_frag_len + L,
+                                                                     min_score.data(), nh, raw_score.data(), sinks.data(), nullptr, hip_stream), ungapped ? "nvbio_hip_hamming_score_qual" : "nvbio_hip_alignment_score_qual");
                     }
                     hip_check(nvbio_hip_opposite_score_finish(nh, nullptr, o_valid.data(), raw_score.data(), sinks.data(), min_score.data(), o_gbegin.data(), worst_score,
                                                               o_score.data(), o_score2.data(), o_loc.data(), o_sink.data(), o_sink2.data(), hip_stream), "nvbio_hip_opposite_score_finish");

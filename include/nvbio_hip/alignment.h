@@ -137,7 +137,36 @@ struct EditDistanceAligner
 template <AlignmentType TYPE> EditDistanceAligner<TYPE> make_edit_distance_aligner() { return EditDistanceAligner<TYPE>(); }
 template <AlignmentType TYPE, typename algorithm_tag> EditDistanceAligner<TYPE, algorithm_tag> make_edit_distance_aligner() { return EditDistanceAligner<TYPE, algorithm_tag>(); }
 
+/// HammingDistanceAligner<TYPE, scheme, algorithm_tag> (alignment_base.h:365-393): ungapped scoring, every border zero.  The scheme is
+/// a SimpleSmithWatermanScheme (match and mismatch are read) or a SmithWatermanScoringScheme with the patterns' quality bytes; only
+/// BatchedAlignmentScore / batch_alignment_score take it, and only with PatternBlockingTag (nvbio_hip_hamming_score, nvbio_hip.h)
+struct HammingDistanceTag {};
+template <AlignmentType T, typename scoring_scheme_type, typename algorithm_tag = PatternBlockingTag>
+struct HammingDistanceAligner
+{
+    static const AlignmentType TYPE = T;
+    typedef HammingDistanceTag  aligner_tag;
+    typedef algorithm_tag       algorithm_type;
+    typedef scoring_scheme_type scoring_scheme;
+    HammingDistanceAligner(const scoring_scheme_type _scheme) : scheme(_scheme) {}
+    scoring_scheme_type scheme;
+};
+template <AlignmentType TYPE, typename scoring_scheme_type>
+HammingDistanceAligner<TYPE, scoring_scheme_type> make_hamming_distance_aligner(const scoring_scheme_type& scheme) { return HammingDistanceAligner<TYPE, scoring_scheme_type>(scheme); }
+template <AlignmentType TYPE, typename scoring_scheme_type, typename algorithm_tag>
+HammingDistanceAligner<TYPE, scoring_scheme_type, algorithm_tag> make_hamming_distance_aligner(const scoring_scheme_type& scheme) { return HammingDistanceAligner<TYPE, scoring_scheme_type, algorithm_tag>(scheme); }
+
 namespace priv {
+/// the ungapped entries, by scheme
+inline int hamming_score(const SimpleSmithWatermanScheme& s, int32 algo, int32 type, const nvbio_hip_string_set& p, const uint8*, uint64, const nvbio_hip_string_set& t,
+                         uint32 maxP, uint32 maxT, const int32* min_score, uint32 n, int32* score, uint32* sink, uint8* ok, void* stream)
+{ const nvbio_hip_sw_scheme sc = { s.m_match, s.m_mismatch, s.m_deletion, s.m_insertion };
+  return nvbio_hip_hamming_score(&sc, algo, type, &p, &t, maxP, maxT, min_score, n, score, sink, ok, stream); }
+template <typename quality_scheme_type>
+inline int hamming_score(const quality_scheme_type& s, int32 algo, int32 type, const nvbio_hip_string_set& p, const uint8* quals, uint64 n_quals, const nvbio_hip_string_set& t,
+                         uint32 maxP, uint32 maxT, const int32* min_score, uint32 n, int32* score, uint32* sink, uint8* ok, void* stream)
+{ const nvbio_hip_gotoh_qual_scheme sc = s.abi();
+  return nvbio_hip_hamming_score_qual(&sc, algo, type, &p, quals, n_quals, &t, maxP, maxT, min_score, n, score, sink, ok, stream); }
 inline nvbio_hip_gotoh_scheme abi_scheme(const SimpleGotohScheme& s) { const nvbio_hip_gotoh_scheme r = { s.m_match, s.m_mismatch, s.m_gap_open, s.m_gap_ext }; return r; }
 inline nvbio_hip_sw_scheme    abi_scheme(const SimpleSmithWatermanScheme& s) { const nvbio_hip_sw_scheme r = { s.m_match, s.m_mismatch, s.m_deletion, s.m_insertion }; return r; }
 /// the C-ABI entry for each scheme kind: Gotoh / linear-gap (SW, ED)
@@ -388,13 +417,21 @@ struct BatchedAlignmentScore
     static uint64 min_temp_storage(const uint32, const uint32, const uint32) { return 0u; }   // no column storage: the
     static uint64 max_temp_storage(const uint32, const uint32, const uint32) { return 0u; }   // pattern lives in a wave's registers
 
-    /// min_score / ok: optional device arrays (the reference's context.min_score and per-job bool)
+    /// min_score / ok: optional device arrays (the reference's context.min_score and per-job bool).  quals / n_quals: the patterns'
+    /// quality bytes, at the patterns' own offsets (an ungapped aligner over a quality scheme reads them)
     void enact(stream_type stream, uint64 temp_size = 0u, uint8* temp = nullptr,
-               const int32* min_score = nullptr, uint8* ok = nullptr, void* hip_stream = nullptr)
+               const int32* min_score = nullptr, uint8* ok = nullptr, void* hip_stream = nullptr, const uint8* quals = nullptr, uint64 n_quals = 0)
     {
         (void)temp_size; (void)temp;
         const nvbio_hip_string_set p = stream.m_patterns.abi(), t = stream.m_texts.abi();
         const bool text_blocking = priv::same_type<typename aligner_type::algorithm_type, TextBlockingTag>::value;
+        if constexpr (priv::same_type<typename aligner_type::aligner_tag, HammingDistanceTag>::value)
+        {
+            hip_check(priv::hamming_score(stream.aligner().scheme, text_blocking ? NVBIO_HIP_TEXT_BLOCKING : NVBIO_HIP_PATTERN_BLOCKING, int32(aligner_type::TYPE), p, quals, n_quals, t,
+                                          stream.max_pattern_length(), stream.max_text_length(), min_score, stream.size(), stream.m_sinks.score, stream.m_sinks.sink, ok, hip_stream),
+                      "nvbio_hip_hamming_score");
+        }
+        else
         hip_check(nvbio_hip_alignment_score(priv::aligner_kind(stream.aligner().scheme), text_blocking ? NVBIO_HIP_TEXT_BLOCKING : NVBIO_HIP_PATTERN_BLOCKING,
                                             priv::scheme4(stream.aligner().scheme).v, int32(aligner_type::TYPE), &p, &t,
                                             stream.max_pattern_length(), stream.max_text_length(),

@@ -120,7 +120,8 @@ SmithWatermanAligner<TYPE, scoring_scheme_type> make_smith_waterman_aligner(cons
 template <AlignmentType TYPE, typename algorithm_tag, typename scoring_scheme_type> NVBIO_FORCEINLINE NVBIO_HOST_DEVICE
 SmithWatermanAligner<TYPE, scoring_scheme_type, algorithm_tag> make_smith_waterman_aligner(const scoring_scheme_type& scheme) { return SmithWatermanAligner<TYPE, scoring_scheme_type, algorithm_tag>(scheme); }
 
-/// ungapped alignment (alignment_base.h:365-393): a value type here -- nvBowtie's scheme names it, no batch function of the hot path takes it
+/// ungapped alignment (alignment_base.h:365-393): priv::hamming_score per thread (alignment.h); BatchedAlignmentScore sends pattern-blocking
+/// streams of it to the tuned kernel behind nvbio_hip_hamming_score / _qual (batched.h: tuned_aligner) -- nvBowtie's --ungapped-mates
 template <AlignmentType T_TYPE, typename scoring_scheme_type, typename AlgorithmType = PatternBlockingTag>
 struct HammingDistanceAligner
 {

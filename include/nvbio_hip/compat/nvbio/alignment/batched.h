@@ -7,7 +7,8 @@
 // enact() picks one of three executions, all producing the reference's results:
 //   * DeviceThreadScheduler, recognised stream: when strings.pattern / strings.text are vector_views over PackedStreams of
 //     32-bit words in device memory (2- or 4-bit patterns, 2-bit texts), the qualities are trivial, the aligner is a
-//     Gotoh / Smith-Waterman / edit-distance aligner over the library's Simple*Scheme and the sink a BestSink<int32>, a
+//     Gotoh / Smith-Waterman / edit-distance / (full-matrix score only) pattern-blocking ungapped aligner over the library's
+//     Simple*Scheme and the sink a BestSink<int32>, a
 //     small kernel evaluates the stream's functors per job into a job table (string offsets, lengths, min_score), the
 //     tuned gfx950 kernels behind the C-ABI (include/nvbio_hip.h) score the table, and a second small kernel hands each
 //     result to stream.output().  init_context() runs in both small kernels; streams are pure functors of i.
@@ -221,6 +222,32 @@ template <AlignmentType T, typename S, typename G> struct tuned_aligner< GotohAl
         }
         q.pattern_gap_open = s.pattern_gap_open(); q.pattern_gap_ext = s.pattern_gap_extension();
         q.text_gap_open = s.text_gap_open();       q.text_gap_ext = s.text_gap_extension();
+        return true;
+    }
+};
+/// the ungapped aligner in its pattern-blocking order -- the one order the tuned kernel walks (nvbio_hip_hamming_score / _qual): over
+/// the library's SimpleSmithWatermanScheme, or over a scheme of nvBowtie's concept (its --ungapped-mates aligners, scoring.h:214-215).
+/// Full-matrix score batches only: the reference has no banded or traceback form of it.  TextBlockingTag streams take the generic lane.
+enum { NVBIO_HIP_COMPAT_HAMMING_ALIGNER = 2 };
+template <AlignmentType T> struct tuned_aligner< HammingDistanceAligner<T, SimpleSmithWatermanScheme, PatternBlockingTag> > {
+    static const bool ok = true; static const bool QUAL = false; static const int32 KIND = NVBIO_HIP_COMPAT_HAMMING_ALIGNER; static const bool TEXT_BLOCKING = false;
+    static void scheme4(const HammingDistanceAligner<T, SimpleSmithWatermanScheme, PatternBlockingTag>& a, int32* v) { v[0] = a.scheme.m_match; v[1] = a.scheme.m_mismatch; v[2] = 0; v[3] = 0; } };
+template <AlignmentType T, typename S> struct tuned_aligner< HammingDistanceAligner<T, S, PatternBlockingTag> > {
+    static const bool ok = quality_scheme<S>::value; static const bool QUAL = true; static const int32 KIND = NVBIO_HIP_COMPAT_HAMMING_ALIGNER; static const bool TEXT_BLOCKING = false;
+    /// false when match(q) depends on the quality or mismatch(r, q, qq) on more than the quality: generic lane
+    static bool table(const HammingDistanceAligner<T, S, PatternBlockingTag>& a, nvbio_hip_gotoh_qual_scheme& q)
+    {
+        const S& s = a.scheme;
+        q.match = s.match(uint8(0));
+        for (uint32 qq = 0; qq < 256u; ++qq)
+        {
+            q.mismatch[qq] = s.mismatch(uint8(0), uint8(1), uint8(qq));
+            if (s.match(uint8(qq)) != q.match) return false;
+            for (uint32 r = 0; r < 5u; ++r)
+                for (uint32 c = 0; c < 5u; ++c)
+                    if (r != c && s.mismatch(uint8(r), uint8(c), uint8(qq)) != q.mismatch[qq]) return false;
+        }
+        q.pattern_gap_open = q.pattern_gap_ext = q.text_gap_open = q.text_gap_ext = 0;      // not read
         return true;
     }
 };
@@ -738,6 +765,14 @@ struct tuned_scheme
     {
         const uint32 n = stream.size(), maxP = maxP_of(stream), maxT = maxT_of(stream);
         const int32 algo = TA::TEXT_BLOCKING ? NVBIO_HIP_TEXT_BLOCKING : NVBIO_HIP_PATTERN_BLOCKING;
+        if constexpr (TA::KIND == 2 /* NVBIO_HIP_COMPAT_HAMMING_ALIGNER */)
+        {
+            // ungapped: every threshold is passed on (the exit test reads it even at -2^30: an empty text's edge lies below)
+            if constexpr (TA::QUAL) return nvbio_hip_hamming_score_qual(&q, algo, int32(aligner_type::TYPE), &ps, quals, n_quals, &ts, maxP, maxT, t.min_score, n, t.score, t.sink, t.ok, hs);
+            else { const nvbio_hip_sw_scheme w = { sc[0], sc[1], sc[2], sc[3] };
+                return nvbio_hip_hamming_score(&w, algo, int32(aligner_type::TYPE), &ps, &ts, maxP, maxT, t.min_score, n, t.score, t.sink, t.ok, hs); }
+        }
+        else
         // thresholds that can never bind are not passed on (a non-negative match score: with a negative one even -2^30 takes part in the
         // reference's exit test for empty patterns, gotoh_inl.h:1203-1207)
         if constexpr (TA::QUAL) return nvbio_hip_alignment_score_qual(&q, algo, int32(aligner_type::TYPE), &ps, quals, n_quals, &ts, maxP, maxT, (t.no_thresholds && q.match >= 0) ? nullptr : t.min_score, n, t.score, t.sink, t.ok, hs);

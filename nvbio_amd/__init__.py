@@ -13,7 +13,8 @@ from .alignment import (GLOBAL, LOCAL, SEMI_GLOBAL, PATTERN_BLOCKING, TEXT_BLOCK
                         BatchedAlignmentScore, batch_alignment_score,
                         BatchedBandedAlignmentTraceback, batch_banded_alignment_traceback, batch_alignment_traceback,
                         SimpleSmithWatermanScheme, SmithWatermanAligner, EditDistanceAligner,
-                        make_smith_waterman_aligner, make_edit_distance_aligner)
+                        make_smith_waterman_aligner, make_edit_distance_aligner,
+                        HammingDistanceAligner, make_hamming_distance_aligner)
 from .fmindex import FMIndexDevice, FMIndexFilter, rank, rank4, rank_range, match, locate, \
     locate_ssa_iterator, lookup_ssa_iterator, build_bwt_occ  # noqa: F401
 from .mapping import MappingParams, map_exact, map_seeds, unpack_seed_hits  # noqa: F401

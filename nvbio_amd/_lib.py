@@ -8,6 +8,7 @@ LIB_PATH = os.path.join(HERE, "lib", "libnvbio_hip.so")
 # every symbol include/nvbio_hip.h declares
 SYMBOLS = [
     "nvbio_hip_banded_gotoh_score", "nvbio_hip_banded_gotoh_score_qual", "nvbio_hip_banded_gotoh_score_qual_views", "nvbio_hip_banded_gotoh_score_qual_bounded", "nvbio_hip_banded_gotoh_score_qual_wave", "nvbio_hip_gotoh_score", "nvbio_hip_banded_sw_score", "nvbio_hip_sw_score", "nvbio_hip_alignment_score", "nvbio_hip_alignment_score_qual", "nvbio_hip_alignment_score_qual_jobs",
+    "nvbio_hip_hamming_score", "nvbio_hip_hamming_score_qual", "nvbio_hip_hamming_score_qual_jobs", "nvbio_hip_hamming_score_host", "nvbio_hip_hamming_score_qual_host",
     "nvbio_hip_banded_gotoh_traceback_temp_bytes", "nvbio_hip_banded_gotoh_traceback", "nvbio_hip_banded_gotoh_traceback_qual",
     "nvbio_hip_gotoh_traceback_temp_bytes", "nvbio_hip_gotoh_traceback", "nvbio_hip_gotoh_traceback_qual", "nvbio_hip_gotoh_traceback_known_score", "nvbio_hip_gotoh_traceback_qual_known_score", "nvbio_hip_known_score_redone", "nvbio_hip_banded_sw_traceback", "nvbio_hip_sw_traceback",
     "nvbio_hip_fm_rank", "nvbio_hip_fm_rank4", "nvbio_hip_fm_rank_range",
@@ -124,6 +125,12 @@ def lib():
                                              vp, vp, vp, vp, u32, vp, vp, u64, vp]
         L.nvbio_hip_alignment_score_qual.argtypes = [P(GotohQualSchemeStruct), i32, i32, P(StringSetStruct), vp, u64, P(StringSetStruct), u32, u32, vp, u32, vp, vp, vp, vp]
         L.nvbio_hip_gotoh_score.argtypes = [P(GotohSchemeStruct), i32, P(StringSetStruct), P(StringSetStruct), u32, u32, vp, u32, vp, vp, vp, vp]
+        L.nvbio_hip_hamming_score.argtypes = [P(GotohSchemeStruct), i32, i32, P(StringSetStruct), P(StringSetStruct), u32, u32, vp, u32, vp, vp, vp, vp]
+        L.nvbio_hip_hamming_score_qual.argtypes = [P(GotohQualSchemeStruct), i32, i32, P(StringSetStruct), vp, u64, P(StringSetStruct), u32, u32, vp, u32, vp, vp, vp, vp]
+        L.nvbio_hip_hamming_score_qual_jobs.argtypes = [P(GotohQualSchemeStruct), i32, i32, P(StringSetStruct), vp, u64, P(StringSetStruct), u32, u32, vp,
+                                                        u32, vp, vp, vp, u32, i32, vp, vp, vp, vp]
+        L.nvbio_hip_hamming_score_host.argtypes = [P(GotohSchemeStruct), i32, i32, P(StringSetStruct), P(StringSetStruct), vp, u32, vp, vp, vp, i32]
+        L.nvbio_hip_hamming_score_qual_host.argtypes = [P(GotohQualSchemeStruct), i32, i32, P(StringSetStruct), vp, u64, P(StringSetStruct), vp, u32, vp, vp, vp, i32]
         L.nvbio_hip_fm_rank.argtypes = [P(FMIndexStruct), vp, vp, u32, vp, vp]
         L.nvbio_hip_fm_rank4.argtypes = [P(FMIndexStruct), vp, u32, vp, vp]
         L.nvbio_hip_fm_rank_range.argtypes = [P(FMIndexStruct), vp, vp, u32, vp, vp]

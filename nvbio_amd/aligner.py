@@ -13,7 +13,7 @@ falls back to the CPU."""
 import torch
 
 from . import mapping, reduce, select as sel
-from .alignment import (make_gotoh_aligner, make_edit_distance_aligner, SmithWatermanScoringScheme, SEMI_GLOBAL, LOCAL, PATTERN_BLOCKING, batch_banded_alignment_score,
+from .alignment import (make_gotoh_aligner, make_edit_distance_aligner, make_hamming_distance_aligner, HammingDistanceAligner, SmithWatermanScoringScheme, SEMI_GLOBAL, LOCAL, PATTERN_BLOCKING, batch_banded_alignment_score,
                         batch_banded_alignment_traceback, batch_alignment_score, batch_alignment_traceback)
 from .strings import PackedStringSet
 
@@ -49,6 +49,7 @@ class Params:
         self.seed_len, self.seed_freq, self.min_read_len = 22, (mapping.SQRT_FUNC, 1.0, 1.15), 12
         self.local = False
         self.scoring_mode = "sw"                       # --scoring sw|ed (params.cpp:117): "ed" extends, reduces and traces hits with the edit-distance aligner
+        self.ungapped_mates = False                    # --ungapped-mates (params.cpp:136; best_approx_paired only): see best_approx_paired
         self.fw, self.rc = True, True
         # paired-end (params.cpp:165-172; io::PE_POLICY_FR)
         self.pe_policy, self.pe_overlap, self.pe_unpaired, self.pe_discordant, self.min_frag_len, self.max_frag_len = 1, True, True, True, 0, 500
@@ -314,7 +315,8 @@ def best_approx_score_paired(fmi, rfmi, state, seed_queue, anchor, best, best_o,
             hit_score, hit_sink = sel.anchor_score_finish(raw, raw_sink, tb, ms, WORST_SCORE)
         with _Stage(stats, "opposite_score"):
             ow = sel.opposite_score_setup(rid, seed, loc, hit_score, WORST_SCORE, best, best_o, scheme, anchor, genome_len, a_fix, o_fix, params.pe_policy,
-                                          params.min_frag_len, params.max_frag_len, params.pe_overlap, WORST_SCORE, table, a_read_len=a_len, o_read_len=o_len)
+                                          params.min_frag_len, params.max_frag_len, params.pe_overlap, WORST_SCORE, table, a_read_len=a_len, o_read_len=o_len,
+                                          ungapped=isinstance(full_aligner, HammingDistanceAligner))
             # jobs whose (window, threshold, strand) equal the pair's last scored job are answered from the memo: the reference
             # re-runs them and absorbs the identical result
             o_out = sel.opposite_outputs(int(loc.numel()), WORST_SCORE, loc.device)
@@ -379,6 +381,11 @@ def best_approx_paired(fmi, rfmi, sym1, sym2, genome_words, genome_len, params=N
     full_aligner = make_gotoh_aligner(aln_type, scheme, PATTERN_BLOCKING)            # nvBowtie's aligners carry the default tag
     tb_banded = make_edit_distance_aligner(aln_type) if ed_mode else banded_aligner
     tb_full = make_edit_distance_aligner(aln_type, PATTERN_BLOCKING) if ed_mode else full_aligner
+    # --ungapped-mates (score_paired.cu:110-137): the opposite mate is scored by the ungapped aligner over the same scheme (scoring.h:214-215), in
+    # a window sized for zero text gaps; the traceback stays the gapped one.  In edit-distance mode the scheme's "ungapped" aligners are the
+    # edit-distance aligners themselves (scoring.h:142-143): nothing changes
+    if params.ungapped_mates and not ed_mode:
+        full_aligner = make_hamming_distance_aligner(aln_type, scheme, PATTERN_BLOCKING)
     band_len = band_length(params.max_dist)
     if mates is not None:
         packed = [(m.reversed, m.fw_rc_words) for m in mates]

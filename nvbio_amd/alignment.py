@@ -133,6 +133,21 @@ def make_edit_distance_aligner(aln_type, algorithm=TEXT_BLOCKING):
     return EditDistanceAligner(aln_type, algorithm)
 
 
+class HammingDistanceAligner:
+    """HammingDistanceAligner<TYPE, scheme, algorithm_tag> (alignment_base.h:365-393): ungapped scoring, every border zero.
+    The scheme is a SimpleSmithWatermanScheme (match and mismatch are read) or nvBowtie's SmithWatermanScoringScheme with `quals`."""
+
+    def __init__(self, aln_type, scheme, algorithm=PATTERN_BLOCKING):
+        assert aln_type in (GLOBAL, LOCAL, SEMI_GLOBAL) and algorithm in (PATTERN_BLOCKING, TEXT_BLOCKING)
+        assert isinstance(scheme, (SimpleSmithWatermanScheme, SmithWatermanScoringScheme))
+        self.type, self.scheme, self.algorithm = aln_type, scheme, algorithm
+
+
+def make_hamming_distance_aligner(aln_type, scheme, algorithm=PATTERN_BLOCKING):
+    """make_hamming_distance_aligner<TYPE>(scheme): the reference's default tag, PatternBlockingTag -- the only one the device entry runs"""
+    return HammingDistanceAligner(aln_type, scheme, algorithm)
+
+
 class BatchedBandedAlignmentScore:
     """BatchedBandedAlignmentScore<BAND_LEN, stream, DeviceThreadBlockScheduler>.
 
@@ -383,6 +398,17 @@ class BatchedAlignmentScore:
             max_text_length = max_text_length or texts.fixed_length
         sc = aligner.scheme.struct()
         ps, ts = patterns.struct(), texts.struct()
+        if isinstance(aligner, HammingDistanceAligner):
+            tail = (int(max_pattern_length), int(max_text_length), C.c_void_p(min_score.data_ptr()) if min_score is not None else None, n,
+                    C.c_void_p(out_score.data_ptr()), C.c_void_p(out_sink.data_ptr()),
+                    C.c_void_p(out_ok.data_ptr()) if out_ok is not None else None, current_stream_ptr())
+            if isinstance(aligner.scheme, SmithWatermanScoringScheme):
+                assert quals is not None and quals.dtype == torch.uint8 and quals.is_cuda and quals.is_contiguous()
+                check(lib().nvbio_hip_hamming_score_qual(C.byref(sc), aligner.algorithm, aligner.type, C.byref(ps), C.c_void_p(quals.data_ptr()), quals.numel(),
+                                                         C.byref(ts), *tail), "nvbio_hip_hamming_score_qual")
+            else:
+                check(lib().nvbio_hip_hamming_score(C.byref(sc), aligner.algorithm, aligner.type, C.byref(ps), C.byref(ts), *tail), "nvbio_hip_hamming_score")
+            return
         if isinstance(aligner.scheme, SmithWatermanScoringScheme):
             assert quals is not None and quals.dtype == torch.uint8 and quals.is_cuda and quals.is_contiguous()
             err = lib().nvbio_hip_alignment_score_qual(

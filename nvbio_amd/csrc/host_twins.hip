@@ -159,6 +159,79 @@ NVB_API int nvbio_hip_alignment_score_host(int32_t aligner, int32_t algorithm, c
     });
 }
 
+namespace {
+
+/// nvBowtie's quality scheme as the ungapped aligner reads it: match(q), mismatch(r, q, qq) = the table's entry for the quality byte
+struct QualLutScheme
+{
+    int32 m_match; const int32* lut;
+    int32 match(const uint8 = 0) const { return m_match; }
+    int32 mismatch(const uint8, const uint8, const uint8 qq) const { return lut[qq]; }
+};
+/// quality bytes of one pattern: quals[begin + j], the last byte for anything past the array (as the device entries clamp)
+struct RtQuals
+{
+    const uint8* q; uint64 begin, n;
+    uint8 operator[](const uint32 j) const { const uint64 k = begin + j; return q[k < n ? k : n - 1u]; }
+};
+
+template <typename scheme_type>
+int hamming_host(const scheme_type& sc, const int32 algorithm, const int32 type, const nvbio_hip_string_set* patterns, const uint8* quals, const uint64 n_quals,
+                 const nvbio_hip_string_set* texts, const int32* min_score, const uint32 n, int32* out_score, uint32* out_sink, uint8_t* out_ok, const int n_threads)
+{
+    if (!valid_set(patterns) || !valid_set(texts)) return hipErrorInvalidValue;
+    if (n && (!out_score || !out_sink)) return hipErrorInvalidValue;
+    if (algorithm != NVBIO_HIP_PATTERN_BLOCKING && algorithm != NVBIO_HIP_TEXT_BLOCKING) return hipErrorInvalidValue;
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#endif
+    auto run = [&](const auto al) {
+        #pragma omp parallel num_threads(threads)
+        {
+            std::vector<int16> column;
+            #pragma omp for schedule(dynamic, 64)
+            for (int64 i = 0; i < int64(n); ++i)
+            {
+                const RtString p = string_of(patterns, uint32(i)), t = string_of(texts, uint32(i));
+                column.resize(size_t(p.len > t.len ? p.len : t.len) + 8u);
+                aln::BestSink<int32> sink;
+                const int32 ms = min_score ? min_score[i] : Field_traits<int32>::min();
+                bool ok;
+                if (quals) { const RtQuals q = { quals, p.begin, n_quals }; ok = aln::alignment_score(al, p, q, t, ms, sink, column.data()); }
+                else       ok = aln::alignment_score(al, p, aln::trivial_quality_string(), t, ms, sink, column.data());
+                out_score[i] = sink.score; out_sink[2 * i] = sink.sink.x; out_sink[2 * i + 1] = sink.sink.y;
+                if (out_ok) out_ok[i] = ok ? 1 : 0;
+            }
+        }
+        return int(hipSuccess);
+    };
+    return with_type(type, [&](auto T) {
+        const aln::AlignmentType TYPE = decltype(T)::value;
+        return algorithm == NVBIO_HIP_TEXT_BLOCKING ? run(aln::HammingDistanceAligner<TYPE, scheme_type, aln::TextBlockingTag>(sc))
+                                                    : run(aln::HammingDistanceAligner<TYPE, scheme_type, aln::PatternBlockingTag>(sc));
+    });
+}
+
+} // namespace
+
+NVB_API int nvbio_hip_hamming_score_host(const nvbio_hip_sw_scheme* scheme, int32_t algorithm, int32_t type,
+                                         const nvbio_hip_string_set* patterns, const nvbio_hip_string_set* texts, const int32_t* min_score,
+                                         uint32_t n, int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok, int32_t n_threads)
+{
+    if (!scheme) return hipErrorInvalidValue;
+    const aln::SimpleSmithWatermanScheme sc(scheme->match, scheme->mismatch, scheme->deletion, scheme->insertion);
+    return hamming_host(sc, algorithm, type, patterns, nullptr, 0, texts, min_score, n, out_score, out_sink, out_ok, n_threads);
+}
+
+NVB_API int nvbio_hip_hamming_score_qual_host(const nvbio_hip_gotoh_qual_scheme* scheme, int32_t algorithm, int32_t type,
+                                              const nvbio_hip_string_set* patterns, const uint8_t* quals, uint64_t n_quals, const nvbio_hip_string_set* texts,
+                                              const int32_t* min_score, uint32_t n, int32_t* out_score, uint32_t* out_sink, uint8_t* out_ok, int32_t n_threads)
+{
+    if (!scheme || (n != 0 && (!quals || n_quals == 0))) return hipErrorInvalidValue;
+    const QualLutScheme sc = { scheme->match, scheme->mismatch };
+    return hamming_host(sc, algorithm, type, patterns, quals, n_quals, texts, min_score, n, out_score, out_sink, out_ok, n_threads);
+}
+
 NVB_API int nvbio_hip_fm_rank_host(const nvbio_hip_fmindex* fmi, const uint32_t* k, const uint8_t* c, uint32_t n, uint32_t* out, int32_t n_threads)
 {
     if (!fmi || !fmi->bwt_occ || (n && (!k || !c || !out))) return hipErrorInvalidValue;

@@ -164,8 +164,11 @@ def anchor_score_finish(raw_score, raw_sink, text_begin, min_score, worst_score)
 
 
 def opposite_score_setup(hit_read_id, hit_seed, hit_loc, hit_score, worst_score, best, best_o, scheme, anchor, genome_len, fixed_read_len, o_fixed_read_len,
-                         pe_policy, min_frag_len, max_frag_len, pe_overlap, score_limit, table=None, a_read_len=None, o_read_len=None):
-    """BestOppositeScoreStream::init_context for the hits of the opposite queue -> dict(valid, min_score, read_rc, genome_begin, genome_end)."""
+                         pe_policy, min_frag_len, max_frag_len, pe_overlap, score_limit, table=None, a_read_len=None, o_read_len=None, ungapped=False):
+    """BestOppositeScoreStream::init_context for the hits of the opposite queue -> dict(valid, min_score, read_rc, genome_begin, genome_end).
+    ungapped: the windows of the ungapped aligner, whose max_text_gaps is 0 -- the window formula opens a text gap and extends it while the
+    threshold holds (utils_inl.h:181-204), so an opening that costs nothing and an extension that no threshold affords count to zero."""
+    text_gap_open, text_gap_ext = (0, -(1 << 29)) if ungapped else (int(scheme.text_gap_open()), int(scheme.text_gap_extension()))
     from ._lib import PeParamsStruct
     n = hit_read_id.numel()
     dev = hit_read_id.device
@@ -176,7 +179,7 @@ def opposite_score_setup(hit_read_id, hit_seed, hit_loc, hit_score, worst_score,
     pp = PeParamsStruct(int(pe_policy), int(min_frag_len), int(max_frag_len), int(bool(pe_overlap)), int(score_limit), int(anchor), int(genome_len))
     check(lib().nvbio_hip_opposite_score_setup(n, _vp(hit_read_id), _vp(hit_seed), _vp(hit_loc), _vp(hit_score), int(worst_score), _vp(a_read_len), _vp(o_read_len),
                                                int(fixed_read_len), int(o_fixed_read_len), _vp(best.data), _vp(best_o.data), best.stride,
-                                               int(scheme.m_match), _vp(table), int(scheme.text_gap_open()), int(scheme.text_gap_extension()), C.byref(pp),
+                                               int(scheme.m_match), _vp(table), text_gap_open, text_gap_ext, C.byref(pp),
                                                _vp(out["valid"]), _vp(out["min_score"]), _vp(out["read_rc"]), _vp(out["genome_begin"]), _vp(out["genome_end"]),
                                                None, 0, None, None, None, current_stream_ptr()), "nvbio_hip_opposite_score_setup")
     table.record_stream(torch.cuda.current_stream())

@@ -74,6 +74,7 @@ def main():
     ap.add_argument("--ns", type=float, default=0.0, help="fraction of read bases replaced by N (single-end modes)")
     ap.add_argument("--quals", default="I", help="one quality character for all bases, or 'random'")
     ap.add_argument("--repeats", type=float, default=0.0, help="fraction of the genome covered by diverged copies of a few repeat families")
+    ap.add_argument("--pair-indels", action="store_true", help="paired mode: apply --indels to the mates too (an indel in the middle of a mate)")
     ap.add_argument("--mixed", action="store_true", help="paired mode: mates of different lengths (70 .. 130 bp each)")
     ap.add_argument("--extra", default="", help="further nvBowtie options, e.g. '-N 1 -L 18'")
     ap.add_argument("--own", default="", help="the same settings for this repository's driver: comma-separated Params fields, e.g. 'allow_sub=1,seed_len=18'")
@@ -136,6 +137,15 @@ def prepare(args):
         else:
             m1 = [mutate(rng, text[p:p + L], 0.02) for p in pos]
             m2 = [mutate(rng, (3 - text[p + f - L:p + f])[::-1], 0.02) for p, f in zip(pos, frag)]
+        if args.indels > 0.0 and getattr(args, "pair_indels", False):
+            # a 1-2 bp insertion or deletion in the middle of either mate (the same shapes as the single-end modes'), drawn after everything
+            # else so that cases without the option keep their reads
+            def indel(m):
+                k, g = int(rng.integers(3 * len(m) // 10, 7 * len(m) // 10)), int(rng.integers(1, 3))
+                return (np.concatenate([m[:k], rng.integers(0, 4, g).astype(np.uint8), m[k:]])[:len(m)] if rng.random() < 0.5
+                        else np.concatenate([m[:k], m[k + g:], rng.integers(0, 4, g).astype(np.uint8)]))
+            m1 = [indel(m) if rng.random() < args.indels else m for m in m1]
+            m2 = [indel(m) if rng.random() < args.indels else m for m in m2]
         f1, f2 = os.path.join(tmp, "m1.fastq"), os.path.join(tmp, "m2.fastq")
         q = getattr(args, "quals", "I")
         write_fastq(f1, m1, "pair", q, rng); write_fastq(f2, m2, "pair", q, rng)
