@@ -942,6 +942,62 @@ int nvbio_hip_fm_filter_locate(const nvbio_hip_fmindex* fmi, const uint32_t* ran
                                uint32_t n_queries, uint64_t begin, uint64_t end,
                                uint32_t* out_hits, void* stream);
 
+/* ---- Bidirectional search and maximal exact matches (nvbio/fmindex/bidir.h, mem.h).  f_fmi indexes the text, r_fmi the reversed
+ * text; both must have the same length.  Only the reference-layout bwt_occ records are read: an index with dimer / ktab attached
+ * gives the same results.
+ *
+ * Replaces extend_forward / extend_backwards (bidir_inl.h:48-144), batched: job i holds the forward range f_ranges[2i..] of a string
+ * P and the range r_ranges[2i..] of P reversed in r_fmi; the outputs are the two ranges of P c[i] (NVBIO_HIP_EXTEND_FORWARD) or of
+ * c[i] P (NVBIO_HIP_EXTEND_BACKWARDS).  The ranges of the empty string are (0, length).  Unlike the reference's, the ranges count
+ * the row of the suffix that is P itself, so they equal what nvbio_hip_fm_match returns for the extended string.
+ * A symbol > 3 gives (1, 0) for both. */
+#define NVBIO_HIP_EXTEND_FORWARD   0
+#define NVBIO_HIP_EXTEND_BACKWARDS 1
+int nvbio_hip_fm_extend(int32_t direction, const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi,
+                        const uint32_t* f_ranges, const uint32_t* r_ranges, const uint8_t* c, uint32_t n,
+                        uint32_t* out_f_ranges, uint32_t* out_r_ranges, void* stream);
+
+/* Replaces MEMFilter<device_tag,fm_index>::rank (mem.h:378-449, mem_inl.h:36-171).  For every string P (2- or 4-bit symbols;
+ * symbols > 3 match nothing) and k = min_intv >= 1: ell(p) is the largest l such that P[p, p+l) holds no symbol > 3 and occurs at
+ * least k times; the k-SMEMs are the spans [p, p + ell(p)) with ell(p) >= 1 that end past the span of p - 1.  One is reported iff
+ * end - begin >= min_span and its SA range holds at most max_intv rows.  Reported MEMs are ordered by string, then by begin.
+ *   out_ranges   4 words per MEM: {sa_begin, sa_end, string_id, begin | end << 16}, the inclusive range of P[begin, end) in f_fmi
+ *   out_index    n + 1 words (uint64): the first MEM of every string, out_index[n] = the number of MEMs
+ *   out_slots    inclusive scan of the range sizes of the stored MEMs (uint64)
+ *   out_n_ranges HOST word: the number of MEMs found, whatever the capacity; the call synchronises the stream to learn it
+ * At most `capacity` MEMs are stored (the sum of the string lengths always suffices); when more were found nothing is written past
+ * it, *out_n_ranges still holds the true number and the call returns NVBIO_HIP_ERROR_CAPACITY: call again with that much room.
+ * No string may be longer than max_pattern_len <= 65535, and n < 2^31: hipErrorInvalidValue (for a length array that holds a longer
+ * string, after the first pass; nothing is stored then and *out_n_ranges is 0).
+ * temp: device scratch of nvbio_hip_fm_mem_temp_bytes(n, max_pattern_len) bytes.  Nearly all of it holds the right ranges a lane keeps
+ * while it walks: 12 * max_pattern_len bytes for each of min(n rounded up to 256, 524288) lanes in flight, whatever the strings'
+ * actual lengths -- 0.95 GB at 150 symbols, 6 GB per 100 k strings of 5 000, and beyond a device's memory for a full grid near the
+ * 65 535 limit.  The size is not negotiable per call: to spend less, rank a long-pattern set in batches of fewer strings. */
+#define NVBIO_HIP_ERROR_CAPACITY 0x10001     /* outside hipError_t's values: never a code of the runtime's */
+uint64_t nvbio_hip_fm_mem_temp_bytes(uint32_t n, uint32_t max_pattern_len);
+int nvbio_hip_fm_mem_rank(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                          uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                          uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                          void* temp, uint64_t temp_bytes, void* stream);
+
+/* Replaces MEMFilter<device_tag,fm_index>::locate (mem_inl.h): out_hits[4(h-begin)..] = {text position, string id, begin, end} for
+ * the global hit indices h in [begin,end) of the n_ranges stored MEMs. */
+int nvbio_hip_fm_mem_locate(const nvbio_hip_fmindex* f_fmi, const uint32_t* ranges, const uint64_t* slots, uint64_t n_ranges,
+                            uint64_t begin, uint64_t end, uint32_t* out_hits, void* stream);
+
+/* Host twins of the three entries above: host pointers everywhere, OpenMP over the jobs, n_threads <= 0 = all.  The rank twin needs
+ * no scratch; out_records, if not NULL, receives the number of 32-byte index records the walks read: per step one for each end of
+ * the range that is a row of the BWT, one for both when they share a record -- what the device kernel loads. */
+int nvbio_hip_fm_extend_host(int32_t direction, const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi,
+                             const uint32_t* f_ranges, const uint32_t* r_ranges, const uint8_t* c, uint32_t n,
+                             uint32_t* out_f_ranges, uint32_t* out_r_ranges, int32_t n_threads);
+int nvbio_hip_fm_mem_rank_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                               uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                               uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                               uint64_t* out_records, int32_t n_threads);
+int nvbio_hip_fm_mem_locate_host(const nvbio_hip_fmindex* f_fmi, const uint32_t* ranges, const uint64_t* slots, uint64_t n_ranges,
+                                 uint64_t begin, uint64_t end, uint32_t* out_hits, int32_t n_threads);
+
 /* Replaces build_occurrence_table<2,64> (nvbio/fmindex/rank_dictionary_inl.h:42-77)
  * fused with the bwt|occ interleave of the loader (fmindex_impl.cu:305-327):
  * bwt_words = big-endian 2-bit BWT, 4*ceil(n/64) words (zero padded);

@@ -6,6 +6,7 @@
 // FMIndexFilterDevice (nvbio/fmindex/filter.h:139-203) with the reference's member names.
 #pragma once
 #include <stdlib.h>
+#include <algorithm>
 #include <string>
 #include "strings.h"
 
@@ -184,6 +185,101 @@ struct FMIndexFilter<device_tag, fm_index_type>
     hip::device_vector<uint8>       d_temp_storage;
 };
 typedef FMIndexFilter<device_tag, fm_index_device> FMIndexFilterDevice;
+
+/// extend_forward / extend_backwards (nvbio/fmindex/bidir.h), batched over device arrays: from the ranges of P in f_fmi and of P reversed
+/// in r_fmi (the index of the reversed text) to those of P c[i] / c[i] P.  The ranges equal match() of the extended string.
+inline void extend_forward(const fm_index_device& f_fmi, const fm_index_device& r_fmi, uint32 n, const uint2* f_ranges, const uint2* r_ranges, const uint8* c,
+                           uint2* out_f_ranges, uint2* out_r_ranges, void* stream = nullptr)
+{ hip_check(nvbio_hip_fm_extend(NVBIO_HIP_EXTEND_FORWARD, &f_fmi.m, &r_fmi.m, reinterpret_cast<const uint32*>(f_ranges), reinterpret_cast<const uint32*>(r_ranges), c, n,
+                                reinterpret_cast<uint32*>(out_f_ranges), reinterpret_cast<uint32*>(out_r_ranges), stream), "nvbio_hip_fm_extend"); }
+inline void extend_backwards(const fm_index_device& f_fmi, const fm_index_device& r_fmi, uint32 n, const uint2* f_ranges, const uint2* r_ranges, const uint8* c,
+                             uint2* out_f_ranges, uint2* out_r_ranges, void* stream = nullptr)
+{ hip_check(nvbio_hip_fm_extend(NVBIO_HIP_EXTEND_BACKWARDS, &f_fmi.m, &r_fmi.m, reinterpret_cast<const uint32*>(f_ranges), reinterpret_cast<const uint32*>(r_ranges), c, n,
+                                reinterpret_cast<uint32*>(out_f_ranges), reinterpret_cast<uint32*>(out_r_ranges), stream), "nvbio_hip_fm_extend"); }
+
+/// MEMFilter<device_tag, fm_index>  (mem.h:378-449): the k-SMEMs of every string of a set, ranked, then located
+template <typename system_tag, typename fm_index_type> struct MEMFilter {};
+
+template <typename fm_index_type>
+struct MEMFilter<device_tag, fm_index_type>
+{
+    typedef device_tag    system_tag;
+    typedef fm_index_type index_type;
+    typedef uint32        coord_type;
+    typedef uint4         rank_type;      ///< {sa_begin, sa_end, string_id, begin | end << 16}
+    typedef uint4         mem_type;       ///< {text position, string id, begin, end}
+    typedef mem_type      hit_type;
+
+    MEMFilter() : m_n_queries(0), m_n_occurrences(0), m_n_ranges(0) {}
+
+    /// find and rank the MEMs of all strings; returns the total number of occurrences.  Room is kept for eight MEMs a string; when the
+    /// library finds more, the call is repeated once with its count.  (The longest string, which the entry wants, is read from the set.)
+    template <typename string_set_type>
+    uint64 rank(const fm_index_type& f_index, const fm_index_type& r_index, const string_set_type& string_set,
+                const uint32 min_intv = 1u, const uint32 max_intv = uint32(-1), const uint32 min_span = 1u)
+    {
+        m_n_queries = string_set.size();
+        uint32 max_pattern_len = 0;
+        {
+            const nvbio_hip_string_set set = string_set.abi();
+            if (!set.length) max_pattern_len = set.fixed_length;
+            else if (m_n_queries)
+            {
+                std::vector<uint32> lengths(m_n_queries);
+                hip_check(nvbio_hip_memcpy(lengths.data(), set.length, uint64(m_n_queries) * 4u, 2, nullptr), "nvbio_hip_memcpy");
+                max_pattern_len = *std::max_element(lengths.begin(), lengths.end());
+            }
+        }
+        m_f_index = f_index; m_r_index = r_index;
+        m_index.resize(uint64(m_n_queries) + 1u);
+        const uint64 tb = nvbio_hip_fm_mem_temp_bytes(m_n_queries, max_pattern_len);
+        if (d_temp_storage.size() < tb) d_temp_storage.resize(tb);
+        const nvbio_hip_string_set s = string_set.abi();
+        uint64 capacity = std::min<uint64>(uint64(m_n_queries) * max_pattern_len, 8ull * m_n_queries + 1024u), found = 0;
+        for (int attempt = 0; attempt < 2; ++attempt)
+        {
+            m_mem_ranges.resize(capacity); m_slots.resize(capacity);
+            const int err = nvbio_hip_fm_mem_rank(&m_f_index.m, &m_r_index.m, &s, m_n_queries, max_pattern_len, min_intv, max_intv, min_span,
+                                                  reinterpret_cast<uint32*>(m_mem_ranges.data()), capacity, m_index.data(), m_slots.data(), &found,
+                                                  d_temp_storage.data(), d_temp_storage.size(), nullptr);
+            if (err != NVBIO_HIP_ERROR_CAPACITY || attempt == 1) { hip_check(err, "nvbio_hip_fm_mem_rank"); break; }
+            capacity = found;
+        }
+        m_n_ranges = found;
+        m_n_occurrences = 0;
+        if (found) hip_check(nvbio_hip_memcpy(&m_n_occurrences, m_slots.data() + (found - 1u), 8, 2, nullptr), "nvbio_hip_memcpy");
+        return m_n_occurrences;
+    }
+    /// global index of the first occurrence of a string's MEMs
+    uint64 first_hit(const uint32 string_id) const
+    {
+        uint64 r = 0, h = 0;
+        hip_check(nvbio_hip_memcpy(&r, m_index.data() + string_id, 8, 2, nullptr), "nvbio_hip_memcpy");
+        if (r) hip_check(nvbio_hip_memcpy(&h, m_slots.data() + (r - 1u), 8, 2, nullptr), "nvbio_hip_memcpy");
+        return h;
+    }
+    /// enumerate the occurrences [begin,end) into device memory
+    void locate(const uint64 begin, const uint64 end, mem_type* mems)
+    {
+        hip_check(nvbio_hip_fm_mem_locate(&m_f_index.m, reinterpret_cast<const uint32*>(m_mem_ranges.data()), m_slots.data(), m_n_ranges,
+                                          begin, end, reinterpret_cast<uint32*>(mems), nullptr), "nvbio_hip_fm_mem_locate");
+    }
+    uint64           n_hits()   const { return m_n_occurrences; }
+    uint64           n_mems()   const { return m_n_occurrences; }
+    uint64           n_ranges() const { return m_n_ranges; }
+    const rank_type* ranges()   const { return m_mem_ranges.data(); }
+    const uint64*    ranks()    const { return m_slots.data(); }
+    const uint64*    index()    const { return m_index.data(); }      ///< first range of every string, n + 1 entries
+
+    uint32                          m_n_queries;
+    index_type                      m_f_index, m_r_index;
+    uint64                          m_n_occurrences, m_n_ranges;
+    hip::device_vector<rank_type>   m_mem_ranges;
+    hip::device_vector<uint64>      m_slots;
+    hip::device_vector<uint64>      m_index;
+    hip::device_vector<uint8>       d_temp_storage;
+};
+typedef MEMFilter<device_tag, fm_index_device> MEMFilterDevice;
 
 /// device build_occurrence_table<2,64> + interleave (rank_dictionary_inl.h:42-77, fmindex_impl.cu:305-327)
 inline void build_bwt_occ(uint32 n, const uint32* d_bwt_words, uint32* d_bwt_occ, uint32 L2_host[5])

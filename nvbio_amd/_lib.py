@@ -28,6 +28,8 @@ SYMBOLS = [
     "nvbio_hip_sort_hits", "nvbio_hip_sort_hits_pingpong", "nvbio_hip_gather_rows", "nvbio_hip_list_flagged", "nvbio_hip_opposite_memo_lookup", "nvbio_hip_opposite_memo_update", "nvbio_hip_traceback_best_known", "nvbio_hip_banded_gotoh_traceback_qual_known",
     "nvbio_hip_fm_locate_ssa_iterator", "nvbio_hip_fm_lookup_ssa_iterator",
     "nvbio_hip_fm_filter_temp_bytes", "nvbio_hip_fm_filter_rank", "nvbio_hip_fm_filter_locate",
+    "nvbio_hip_fm_extend", "nvbio_hip_fm_mem_temp_bytes", "nvbio_hip_fm_mem_rank", "nvbio_hip_fm_mem_locate",
+    "nvbio_hip_fm_extend_host", "nvbio_hip_fm_mem_rank_host", "nvbio_hip_fm_mem_locate_host",
     "nvbio_hip_build_bwt_occ_temp_bytes", "nvbio_hip_build_bwt_occ",
     "nvbio_hip_device_malloc", "nvbio_hip_device_free", "nvbio_hip_device_free_ordered", "nvbio_hip_device_free_after", "nvbio_hip_device_trim", "nvbio_hip_device_mem_info", "nvbio_hip_memcpy", "nvbio_hip_memset",
     "nvbio_hip_stream_synchronize", "nvbio_hip_stream_query", "nvbio_hip_host_malloc", "nvbio_hip_host_free", "nvbio_hip_stream_create", "nvbio_hip_stream_destroy",
@@ -69,6 +71,7 @@ class FMIndexStruct(C.Structure):        # nvbio_hip_fmindex
 
 _lib = None
 ABI_VERSION = 2
+ERROR_CAPACITY = 0x10001      # NVBIO_HIP_ERROR_CAPACITY: nvbio_hip_fm_mem_rank found more MEMs than it was given room for
 
 
 def lib():
@@ -208,6 +211,14 @@ def lib():
         L.nvbio_hip_fm_filter_temp_bytes.restype = u64
         L.nvbio_hip_fm_filter_rank.argtypes = [P(FMIndexStruct), P(StringSetStruct), u32, vp, vp, vp, u64, vp]
         L.nvbio_hip_fm_filter_locate.argtypes = [P(FMIndexStruct), vp, vp, u32, u64, u64, vp, vp]
+        L.nvbio_hip_fm_extend.argtypes = [i32, P(FMIndexStruct), P(FMIndexStruct), vp, vp, vp, u32, vp, vp, vp]
+        L.nvbio_hip_fm_mem_temp_bytes.argtypes = [u32, u32]
+        L.nvbio_hip_fm_mem_temp_bytes.restype = u64
+        L.nvbio_hip_fm_mem_rank.argtypes = [P(FMIndexStruct), P(FMIndexStruct), P(StringSetStruct), u32, u32, u32, u32, u32, vp, u64, vp, vp, P(u64), vp, u64, vp]
+        L.nvbio_hip_fm_mem_locate.argtypes = [P(FMIndexStruct), vp, vp, u64, u64, u64, vp, vp]
+        L.nvbio_hip_fm_extend_host.argtypes = [i32, P(FMIndexStruct), P(FMIndexStruct), vp, vp, vp, u32, vp, vp, i32]
+        L.nvbio_hip_fm_mem_rank_host.argtypes = [P(FMIndexStruct), P(FMIndexStruct), P(StringSetStruct), u32, u32, u32, u32, u32, vp, u64, vp, vp, P(u64), P(u64), i32]
+        L.nvbio_hip_fm_mem_locate_host.argtypes = [P(FMIndexStruct), vp, vp, u64, u64, u64, vp, i32]
         L.nvbio_hip_build_bwt_occ_temp_bytes.argtypes = [u32]
         L.nvbio_hip_build_bwt_occ_temp_bytes.restype = u64
         L.nvbio_hip_build_bwt_occ.argtypes = [u32, vp, vp, vp, vp, u64, vp]

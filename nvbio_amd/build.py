@@ -37,6 +37,15 @@ def _stale(target, srcs):
     return any(os.path.getmtime(s) > t for s in srcs)
 
 
+def _pool_size():
+    """compilers to run at a time: MAX_JOBS when it is set to a positive number, else one per CPU"""
+    try:
+        jobs = int(os.environ.get("MAX_JOBS", "0"))
+    except ValueError:
+        jobs = 0
+    return jobs if jobs > 0 else (os.cpu_count() or 1)
+
+
 def build(force=False, verbose=False):
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(LIBDIR, "obj")
@@ -55,7 +64,7 @@ def build(force=False, verbose=False):
         subprocess.check_call(cmd)
 
     if jobs:
-        with ThreadPoolExecutor(max_workers=min(len(jobs), os.cpu_count() or 1)) as ex:
+        with ThreadPoolExecutor(max_workers=min(len(jobs), _pool_size())) as ex:
             list(ex.map(run, jobs))
     if jobs or force or _stale(LIB, objs):
         run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-fopenmp", "-o", LIB] + objs + ["-ldl"])

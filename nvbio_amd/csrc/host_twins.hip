@@ -8,6 +8,7 @@
 #include "common.h"
 #include "../../include/nvbio_hip/compat/nvbio/alignment/alignment.h"
 #include "../../include/nvbio_hip/compat/nvbio/fmindex/fmindex.h"
+#include "../../include/nvbio_hip/compat/nvbio/fmindex/mem.h"
 #include "../../include/nvbio_hip/compat/nvbio/basic/deinterleaved_iterator.h"
 #if defined(_OPENMP)
 #include <omp.h>
@@ -270,5 +271,105 @@ NVB_API int nvbio_hip_fm_locate_host(const nvbio_hip_fmindex* fmi, const uint32_
 #endif
     #pragma omp parallel for schedule(dynamic, 1024) num_threads(threads)
     for (int64 i = 0; i < int64(n); ++i) out_pos[i] = locate(f, sa_rows[i]);
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------- bidirectional search, MEMs
+NVB_API int nvbio_hip_fm_extend_host(int32_t direction, const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi,
+                                     const uint32_t* f_ranges, const uint32_t* r_ranges, const uint8_t* c, uint32_t n,
+                                     uint32_t* out_f_ranges, uint32_t* out_r_ranges, int32_t n_threads)
+{
+    if (!f_fmi || !r_fmi || !f_fmi->bwt_occ || !r_fmi->bwt_occ || f_fmi->length != r_fmi->length) return hipErrorInvalidValue;
+    if (direction != NVBIO_HIP_EXTEND_FORWARD && direction != NVBIO_HIP_EXTEND_BACKWARDS) return hipErrorInvalidValue;
+    if (n && (!f_ranges || !r_ranges || !c || !out_f_ranges || !out_r_ranges)) return hipErrorInvalidValue;
+    const fmi_t f = host_index(f_fmi), r = host_index(r_fmi);
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#endif
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 i = 0; i < int64(n); ++i)
+    {
+        uint2 fr = make_uint2(f_ranges[2 * i], f_ranges[2 * i + 1]), rr = make_uint2(r_ranges[2 * i], r_ranges[2 * i + 1]);
+        if (c[i] > 3u) { fr = make_uint2(1u, 0u); rr = fr; }
+        else if (direction == NVBIO_HIP_EXTEND_FORWARD) extend_forward(f, r, fr, rr, c[i]);
+        else                                            extend_backwards(f, r, fr, rr, c[i]);
+        out_f_ranges[2 * i] = fr.x; out_f_ranges[2 * i + 1] = fr.y; out_r_ranges[2 * i] = rr.x; out_r_ranges[2 * i + 1] = rr.y;
+    }
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_fm_mem_rank_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                                       uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                                       uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                                       uint64_t* out_records, int32_t n_threads)
+{
+    if (!f_fmi || !r_fmi || !f_fmi->bwt_occ || !r_fmi->bwt_occ || f_fmi->length != r_fmi->length) return hipErrorInvalidValue;
+    if (!out_index || !out_n_ranges || min_intv == 0u) return hipErrorInvalidValue;
+    if (n >= 0x80000000u || max_pattern_len > 65535u) return hipErrorInvalidValue;
+    if (capacity != 0u && (!out_ranges || !out_slots)) return hipErrorInvalidValue;
+    *out_n_ranges = 0;
+    if (out_records) *out_records = 0;
+    out_index[0] = 0;
+    if (n == 0 || max_pattern_len == 0) { for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = 0; return hipSuccess; }
+    if (!strings || !strings->words || !strings->begin || strings->n_words == 0) return hipErrorInvalidValue;
+    if (!(strings->bits == 2 || strings->bits == 4)) return hipErrorNotSupported;
+    if (!strings->length && strings->fixed_length > max_pattern_len) return hipErrorInvalidValue;
+    if (strings->length) for (uint32 i = 0; i < n; ++i) if (strings->length[i] > max_pattern_len) return hipErrorInvalidValue;
+    const fmi_t f = host_index(f_fmi), r = host_index(r_fmi);
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#endif
+    std::vector< std::vector< MEMRange<uint32> > > found(n);
+    uint64 records = 0;
+    #pragma omp parallel num_threads(threads) reduction(+ : records)
+    {
+        std::vector<uint4> store;
+        #pragma omp for schedule(dynamic, 256)
+        for (int64 i = 0; i < int64(n); ++i)
+        {
+            const RtString s = string_of(strings, uint32(i));
+            const uint32 len = s.len < max_pattern_len ? s.len : max_pattern_len;
+            fmindex::string_mems(s, len, uint32(i), f, r, min_intv, max_intv, min_span, found[i], store, &records);
+        }
+    }
+    for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = out_index[i] + found[i].size();
+    uint64 sum = 0;
+    for (uint32 i = 0; i < n; ++i)
+        for (size_t k = 0; k < found[i].size(); ++k)
+        {
+            const uint64 at = out_index[i] + k;
+            if (at >= capacity) break;
+            const uint4 v = found[i][k].coords;
+            out_ranges[4 * at] = v.x; out_ranges[4 * at + 1] = v.y; out_ranges[4 * at + 2] = v.z; out_ranges[4 * at + 3] = v.w;
+            sum += uint64(found[i][k].range_size()); out_slots[at] = sum;
+        }
+    *out_n_ranges = out_index[n];
+    if (out_records) *out_records = records;
+    return out_index[n] > capacity ? NVBIO_HIP_ERROR_CAPACITY : int(hipSuccess);
+}
+
+NVB_API int nvbio_hip_fm_mem_locate_host(const nvbio_hip_fmindex* f_fmi, const uint32_t* ranges, const uint64_t* slots, uint64_t n_ranges,
+                                         uint64_t begin, uint64_t end, uint32_t* out_hits, int32_t n_threads)
+{
+    if (!f_fmi || !f_fmi->bwt_occ || !f_fmi->ssa || f_fmi->sa_int == 0 || (f_fmi->sa_int & (f_fmi->sa_int - 1)) != 0) return hipErrorInvalidValue;
+    if (end < begin) return hipErrorInvalidValue;
+    if (end == begin) return hipSuccess;
+    if (!ranges || !slots || !out_hits || n_ranges == 0) return hipErrorInvalidValue;
+    const fmi_t f = host_index(f_fmi);
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#endif
+    #pragma omp parallel for schedule(dynamic, 1024) num_threads(threads)
+    for (int64 h = 0; h < int64(end - begin); ++h)
+    {
+        const uint64 g = begin + uint64(h);
+        uint64 lo = 0, hi = n_ranges;
+        while (lo < hi) { const uint64 mid = lo + (hi - lo) / 2u; if (slots[mid] <= g) lo = mid + 1u; else hi = mid; }
+        uint32* o = out_hits + 4 * h;
+        if (lo >= n_ranges) { o[0] = o[1] = 0xFFFFFFFFu; o[2] = o[3] = 0u; continue; }
+        const uint32* rg = ranges + 4 * lo;
+        o[0] = locate(f, uint32(rg[0] + uint32(g - (lo ? slots[lo - 1u] : 0u))));
+        o[1] = rg[2] & 0x7FFFFFFFu; o[2] = rg[3] & 0xFFFFu; o[3] = rg[3] >> 16;
+    }
     return hipSuccess;
 }

@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from ._lib import lib, check, FMIndexStruct, current_stream_ptr
+from ._lib import lib, check, FMIndexStruct, current_stream_ptr, ERROR_CAPACITY
 
 
 def _vp(t):
@@ -257,6 +257,101 @@ class FMIndexFilter:
         check(lib().nvbio_hip_fm_filter_locate(C.byref(s), _vp(self.ranges), _vp(self.slots), self.n_queries,
                                               begin, end, _vp(hits), current_stream_ptr()), "nvbio_hip_fm_filter_locate")
         return hits
+
+
+def _extend(direction, f_index, r_index, f_ranges, r_ranges, c):
+    n = c.numel()
+    out_f = torch.empty((n, 2), dtype=torch.int32, device=c.device)
+    out_r = torch.empty((n, 2), dtype=torch.int32, device=c.device)
+    fs, rs = f_index.struct(), r_index.struct()
+    check(lib().nvbio_hip_fm_extend(direction, C.byref(fs), C.byref(rs), _vp(f_ranges), _vp(r_ranges), _vp(c), n, _vp(out_f), _vp(out_r),
+                                    current_stream_ptr()), "nvbio_hip_fm_extend")
+    return out_f, out_r
+
+
+def extend_forward(f_index, r_index, f_ranges, r_ranges, c):
+    """extend_forward (nvbio/fmindex/bidir.h), batched: from the ranges of P in the forward index and of P reversed in the index of
+    the reversed text (int32 [n, 2] each; (0, length) for the empty string) to those of P c[i] (c: uint8 [n]).  -> (f_ranges, r_ranges).
+    The ranges count the row of the suffix that is P itself, so they equal match() of the extended string."""
+    return _extend(0, f_index, r_index, f_ranges, r_ranges, c)
+
+
+def extend_backwards(f_index, r_index, f_ranges, r_ranges, c):
+    """extend_backwards (nvbio/fmindex/bidir.h), batched: the ranges of c[i] P.  -> (f_ranges, r_ranges)"""
+    return _extend(1, f_index, r_index, f_ranges, r_ranges, c)
+
+
+class MEMFilter:
+    """MEMFilter<device_tag, fm_index> (nvbio/fmindex/mem.h:378-449): the maximal exact matches of every string of a set on a
+    bidirectional FM-index.  rank() finds the k-SMEMs (k = min_intv) that are at least min_span long and whose SA range holds at
+    most max_intv rows, ordered by string and begin; locate() enumerates their occurrences."""
+
+    def __init__(self):
+        self.n_queries = 0
+        self.n_occurrences = 0
+        self.ranges = None      # int32 [n_ranges, 4]: {sa_begin, sa_end, string_id, begin | end << 16}
+        self.slots = None       # int64 [n_ranges]: inclusive scan of the range sizes
+        self.index = None       # int64 [n + 1]: the first range of every string
+        self.f_index = None
+        self.r_index = None
+
+    def rank(self, f_index, r_index, string_set, min_intv=1, max_intv=0xFFFFFFFF, min_span=1, capacity=None):
+        """-> the total number of MEM occurrences.  `capacity`: room for the ranges, by default eight a string (never more than
+        the sum of the string lengths, which cannot be too small); when the library finds more, the call is repeated once with the
+        number it found."""
+        n = len(string_set)
+        dev = string_set.words.device
+        self.f_index, self.r_index, self.n_queries = f_index, r_index, n
+        if string_set.length is not None:
+            max_len = int(string_set.length.max().item()) if n else 0
+            total_len = int(string_set.length.sum().item()) if n else 0
+        else:
+            max_len, total_len = string_set.fixed_length, n * string_set.fixed_length
+        if capacity is None:
+            capacity = min(total_len, 8 * n + 1024)
+        L = lib()
+        tb = int(L.nvbio_hip_fm_mem_temp_bytes(n, max_len))
+        temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+        self.index = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        fs, rs, ss = f_index.struct(), r_index.struct(), string_set.struct()
+        found = C.c_uint64(0)
+        cap = int(capacity)
+        for _ in range(2):      # at most one retry, with the number the first call found
+            self.ranges = torch.empty((cap, 4), dtype=torch.int32, device=dev)
+            self.slots = torch.empty(cap, dtype=torch.int64, device=dev)
+            err = L.nvbio_hip_fm_mem_rank(C.byref(fs), C.byref(rs), C.byref(ss), n, max_len, min_intv, max_intv, min_span,
+                                          _vp(self.ranges), cap, _vp(self.index), _vp(self.slots), C.byref(found), _vp(temp), tb,
+                                          current_stream_ptr())
+            if err != ERROR_CAPACITY:
+                break
+            cap = int(found.value)
+        check(err, "nvbio_hip_fm_mem_rank")
+        k = int(found.value)
+        self.ranges, self.slots = self.ranges[:k], self.slots[:k]
+        self.n_occurrences = int(self.slots[k - 1].item()) if k else 0
+        return self.n_occurrences
+
+    def n_ranges(self):
+        return int(self.slots.numel())
+
+    def n_mems(self):
+        return self.n_occurrences
+
+    n_hits = n_mems
+
+    def first_hit(self, string_id):
+        """global index of the first occurrence of string `string_id`'s MEMs"""
+        r = int(self.index[string_id].item())
+        return int(self.slots[r - 1].item()) if r else 0
+
+    def locate(self, begin, end, out=None):
+        """-> int32 [end - begin, 4]: {text position, string id, begin, end} of the global occurrences [begin, end)"""
+        if out is None:
+            out = torch.empty((end - begin, 4), dtype=torch.int32, device=self.index.device)
+        s = self.f_index.struct()
+        check(lib().nvbio_hip_fm_mem_locate(C.byref(s), _vp(self.ranges), _vp(self.slots), self.n_ranges(), begin, end, _vp(out),
+                                           current_stream_ptr()), "nvbio_hip_fm_mem_locate")
+        return out
 
 
 def build_bwt_occ(n, bwt_words):
