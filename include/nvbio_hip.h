@@ -998,6 +998,33 @@ int nvbio_hip_fm_mem_rank_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_f
 int nvbio_hip_fm_mem_locate_host(const nvbio_hip_fmindex* f_fmi, const uint32_t* ranges, const uint64_t* slots, uint64_t n_ranges,
                                  uint64_t begin, uint64_t end, uint32_t* out_hits, int32_t n_threads);
 
+/* MEMFilter::rank with its last two arguments, split_len and split_width: BWA-MEM re-seeding over the contract above.
+ * B = what nvbio_hip_fm_mem_rank reports for (min_intv, max_intv, min_span).  A MEM [b, e) of B with e - b >= split_len whose SA range
+ * holds occ <= split_width rows is a candidate; its re-seeds are the (occ + 1)-SMEMs of the string that cover m = (b + e) >> 1
+ * (begin <= m < end; they may reach outside [b, e)), kept iff end - begin >= min_span and at most max_intv rows.  Re-seeds are not split
+ * again.  A string's output is B and the re-seeds of all its candidates, every span once, ordered by begin, then by end: begins can
+ * repeat and ends are not monotone.  The split MEM stays (the reference replaces it).  Records, out_index and out_slots are as above,
+ * and nvbio_hip_fm_mem_locate takes the result.
+ * split_len == 0xFFFFFFFF: no re-seeding; the call IS nvbio_hip_fm_mem_rank, capacity protocol included.
+ * Otherwise the sum of the string lengths no longer bounds the output, and the spans are staged in temp before duplicates go: the call
+ * succeeds iff the number of spans found, a span counted once for every way it was found, is at most `capacity`; then *out_n_ranges is
+ * the number stored.  If not, it returns NVBIO_HIP_ERROR_CAPACITY with that number in *out_n_ranges -- a capacity that suffices -- and
+ * the contents of out_ranges, out_index and out_slots are unspecified; nothing is ever written past `capacity`.
+ * temp: nvbio_hip_fm_mem_split_temp_bytes(n, max_pattern_len, capacity) bytes: twice the kept-range scratch of the plain entry (a
+ * re-seed walks while its candidate's group is still being read) and 16 bytes per unit of capacity.
+ * The host twin follows the same protocol, so the two agree in every word they return. */
+uint64_t nvbio_hip_fm_mem_split_temp_bytes(uint32_t n, uint32_t max_pattern_len, uint64_t capacity);
+int nvbio_hip_fm_mem_rank_split(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                                uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                                uint32_t split_len, uint32_t split_width,
+                                uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                                void* temp, uint64_t temp_bytes, void* stream);
+int nvbio_hip_fm_mem_rank_split_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                                     uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                                     uint32_t split_len, uint32_t split_width,
+                                     uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                                     uint64_t* out_records, int32_t n_threads);
+
 /* Replaces build_occurrence_table<2,64> (nvbio/fmindex/rank_dictionary_inl.h:42-77)
  * fused with the bwt|occ interleave of the loader (fmindex_impl.cu:305-327):
  * bwt_words = big-endian 2-bit BWT, 4*ceil(n/64) words (zero padded);

@@ -1,5 +1,5 @@
 // compat/nvbio/fmindex/mem.h -- maximal exact matches on a bidirectional FM-index (nvbio/fmindex/mem.h, mem_inl.h): find_kmems,
-// MEMRange / MEMHit and MEMFilter<host_tag | device_tag, fm_index> (MEMFilterHost / MEMFilterDevice): rank(f_index, r_index, string_set, min_intv, max_intv, min_span) finds the
+// MEMRange / MEMHit and MEMFilter<host_tag | device_tag, fm_index> (MEMFilterHost / MEMFilterDevice): rank(f_index, r_index, string_set, min_intv, max_intv, min_span, split_len, split_width) finds the
 // k-SMEMs of every string and ranks their SA ranges, locate(begin, end, mems) enumerates the global hits [begin, end) as
 // (text position, string id, span begin, span end).
 //
@@ -11,10 +11,14 @@
 // Deviations from the reference: the start row (above); a right extension whose range never changes size after its first symbol is
 // reported (the reference pushes its last range only after an earlier one, mem_inl.h:92); spans keep 16 bits of `begin`
 // (the reference's span() masks it to 8, mem.h:220) and nothing is dropped past 1 024 ranges (mem_inl.h:381-382).
-// split_len / split_width and find_threshold_kmems are not provided.
+// rank's split_len / split_width re-seed in BWA-MEM's sense, by definition as well: a reported MEM at least split_len long whose range
+// holds occ <= split_width rows is kept, and the (occ + 1)-SMEMs covering its midpoint that pass min_span and max_intv are added, every
+// span once, ordered by begin, then end (the reference replaces the MEM and takes the begins at another threshold than the ends, mem_inl.h:1364-1424).
+// find_threshold_kmems is not provided.
 #pragma once
 #include "bidir.h"
 #include "filter.h"
+#include <algorithm>
 #include <vector>
 
 namespace nvbio {
@@ -168,6 +172,96 @@ void string_mems(const string_type& s, const uint32 len, const uint32 string_id,
     }
 }
 
+// ---- re-seeding (split_len / split_width): a reported MEM [b, e) at least split_len long with occ <= split_width rows is a
+// candidate; its re-seeds are the (occ + 1)-SMEMs covering (b + e) >> 1 -- one find_kmems at that symbol and threshold -- kept iff
+// they pass min_span and max_intv.  The spans go to a `sink` (output(range, span)) that makes the union.
+
+/// the delegate of a re-seed: applies max_intv and hands the span to the sink
+template <typename coord_type, typename sink_type>
+struct mem_reseed_handler
+{
+    typedef typename vector_type<coord_type, 2u>::type range_type;
+    NVBIO_FORCEINLINE NVBIO_HOST_DEVICE mem_reseed_handler(sink_type& s, const uint32 max_intv_) : sink(s), max_intv(max_intv_) {}
+    NVBIO_FORCEINLINE NVBIO_HOST_DEVICE void output(const range_type range, const uint2 span)
+    {
+        if (uint64(coord_type(coord_type(1u) + range.y - range.x)) <= uint64(max_intv)) sink.output(range, span);
+    }
+    sink_type& sink; uint32 max_intv;
+};
+
+/// the delegate of the base walk: applies max_intv, hands the MEM to the sink and, if it is a candidate, re-seeds it at once.
+/// `store2` keeps the re-seed's right ranges (the base group's are still being read): room for pattern_len of them.
+template <typename pattern_type, typename fm_index_type, typename sink_type, typename store_type>
+struct mem_split_handler
+{
+    typedef typename fm_index_type::index_type coord_type;
+    typedef typename fm_index_type::range_type range_type;
+    NVBIO_FORCEINLINE NVBIO_HOST_DEVICE
+    mem_split_handler(const uint32 len_, const pattern_type& pattern_, const fm_index_type& f, const fm_index_type& r, sink_type& sink_, store_type& store2_,
+                      const uint32 max_intv_, const uint32 min_span_, const uint32 split_len_, const uint32 split_width_, uint64* n_records_) :
+        len(len_), pattern(pattern_), f_index(f), r_index(r), sink(sink_), store2(store2_),
+        max_intv(max_intv_), min_span(min_span_), split_len(split_len_), split_width(split_width_), n_records(n_records_) {}
+
+    NVBIO_FORCEINLINE NVBIO_HOST_DEVICE void output(const range_type range, const uint2 span)
+    {
+        const coord_type occ = coord_type(coord_type(1u) + range.y - range.x);
+        if (uint64(occ) > uint64(max_intv)) return;
+        sink.output(range, span);
+        if (span.y - span.x < split_len || uint64(occ) > uint64(split_width)) return;
+        const uint32 k = uint64(occ) >= 0xFFFFFFFFull ? 0xFFFFFFFFu : uint32(occ) + 1u;      // cannot wrap
+        mem_reseed_handler<coord_type, sink_type> reseed(sink, max_intv);
+        find_kmems(len, pattern, (span.x + span.y) >> 1, f_index, r_index, reseed, k, min_span, store2, n_records);
+    }
+    const uint32 len; const pattern_type& pattern; const fm_index_type& f_index; const fm_index_type& r_index; sink_type& sink; store_type& store2;
+    const uint32 max_intv, min_span, split_len, split_width; uint64* n_records;
+};
+
+/// begin, then end, of a span as one ordered key
+NVBIO_FORCEINLINE NVBIO_HOST_DEVICE uint32 span_key(const uint32 w) { return (w << 16) | (w >> 16); }
+
+/// a host sink: every span as it comes
+template <typename coord_type>
+struct mem_vector_sink
+{
+    typedef typename vector_type<coord_type, 2u>::type range_type;
+    mem_vector_sink(std::vector< MEMRange<coord_type> >& out, const uint32 id) : ranges(out), string_id(id) {}
+    void output(const range_type range, const uint2 span) { ranges.push_back(MEMRange<coord_type>(range, string_id, span)); }
+    std::vector< MEMRange<coord_type> >& ranges; uint32 string_id;
+};
+template <typename coord_type>
+struct mem_span_less
+{
+    bool operator() (const MEMRange<coord_type>& a, const MEMRange<coord_type>& b) const { return span_key(uint32(a.coords.w)) < span_key(uint32(b.coords.w)); }
+};
+
+/// every reported MEM of a string and the re-seeds of its candidates appended to `out`, each span once, ordered by begin, then
+/// end; returns the number of spans found before the duplicates were removed
+template <typename string_type, typename fm_index_type>
+uint64 string_mems_split(const string_type& s, const uint32 len, const uint32 string_id, const fm_index_type& f_index, const fm_index_type& r_index,
+                         const uint32 min_intv, const uint32 max_intv, const uint32 min_span, const uint32 split_len, const uint32 split_width,
+                         std::vector< MEMRange<typename fm_index_type::index_type> >& out, std::vector<uint4>& store, std::vector<uint4>& store2, uint64* n_records = NULL)
+{
+    typedef typename fm_index_type::index_type coord_type;
+    typedef mem_vector_sink<coord_type>        sink_type;
+    const size_t first = out.size();
+    sink_type sink(out, string_id);
+    if (store.size()  < size_t(len) + 1u) store.resize(size_t(len) + 1u);
+    if (store2.size() < size_t(len) + 1u) store2.resize(size_t(len) + 1u);
+    mem_split_handler<string_type, fm_index_type, sink_type, std::vector<uint4> > handler(len, s, f_index, r_index, sink, store2, max_intv, min_span, split_len, split_width, n_records);
+    for (uint32 x = 0; x < len;)
+    {
+        const uint32 e = find_kmems(len, s, x, f_index, r_index, handler, min_intv, min_span, store, n_records);
+        x = e > x + 1u ? e : x + 1u;
+    }
+    const uint64 found = out.size() - first;
+    std::sort(out.begin() + first, out.end(), mem_span_less<coord_type>());
+    size_t kept = first;
+    for (size_t k = first; k < out.size(); ++k)
+        if (k == first || out[k].coords.w != out[k - 1u].coords.w) out[kept++] = out[k];
+    out.resize(kept);
+    return found;
+}
+
 } // namespace fmindex
 
 template <typename system_tag, typename fm_index_type> struct MEMFilter {};
@@ -189,7 +283,8 @@ struct MEMFilter<host_tag, fm_index_type>
     /// returns the total number of MEM occurrences
     template <typename string_set_type>
     uint64 rank(const fm_index_type& f_index, const fm_index_type& r_index, const string_set_type& string_set,
-                const uint32 min_intv = 1u, const uint32 max_intv = uint32(-1), const uint32 min_span = 1u)
+                const uint32 min_intv = 1u, const uint32 max_intv = uint32(-1), const uint32 min_span = 1u,
+                const uint32 split_len = uint32(-1), const uint32 split_width = uint32(-1))
     {
         m_n_queries = string_set.size();
         m_f_index = f_index; m_r_index = r_index;
@@ -197,13 +292,17 @@ struct MEMFilter<host_tag, fm_index_type>
         std::vector< std::vector<rank_type> > per_string(m_n_queries);
         #pragma omp parallel
         {
-            std::vector<uint4> store;
+            std::vector<uint4> store, store2;
             #pragma omp for schedule(dynamic, 256)
             for (int64 q = 0; q < n; ++q)
             {
                 const typename string_set_type::string_type s = string_set[uint32(q)];
                 if (length(s) > 65535u) continue;       // refused below
-                fmindex::string_mems(s, uint32(length(s)), uint32(q), m_f_index, m_r_index, min_intv ? min_intv : 1u, max_intv, min_span, per_string[q], store);
+                if (split_len == uint32(-1))
+                    fmindex::string_mems(s, uint32(length(s)), uint32(q), m_f_index, m_r_index, min_intv ? min_intv : 1u, max_intv, min_span, per_string[q], store);
+                else
+                    fmindex::string_mems_split(s, uint32(length(s)), uint32(q), m_f_index, m_r_index, min_intv ? min_intv : 1u, max_intv, min_span, split_len, split_width,
+                                               per_string[q], store, store2);
             }
         }
         m_index.assign(m_n_queries + 1u, 0u);
@@ -306,6 +405,72 @@ __global__ void __launch_bounds__(128) mem_rank_kernel(const uint32 n, const ind
     }
     if (!index) counts[q] = handler.n;
 }
+/// the sink of a re-seeding lane: counts every span and, given the string's segment of the staging table, puts it at its place
+/// by (begin, end) unless it is there already -- from the back: the base MEMs come in order, a re-seed lands near its candidate
+template <typename coord_type>
+struct mem_lane_sink
+{
+    typedef typename vector_type<coord_type, 2u>::type range_type;
+    MEMRange<coord_type>* seg; uint32 raw, kept, string_id;
+    NVBIO_FORCEINLINE NVBIO_HOST_DEVICE void output(const range_type range, const uint2 span)
+    {
+        ++raw;
+        if (!seg) return;
+        const uint32 key = span_key(span.x | (span.y << 16));
+        uint32 p = kept;
+        for (; p > 0u; --p)
+        {
+            const uint32 other = span_key(uint32(seg[p - 1u].coords.w));
+            if (other == key) return;
+            if (other < key) break;
+        }
+        for (uint32 k = kept; k > p; --k) seg[k] = seg[k - 1u];
+        seg[p] = MEMRange<coord_type>(range, string_id, span);
+        ++kept;
+    }
+};
+/// one lane per string: the walk of find_kmems, every candidate re-seeded as it is reported.  raw_index == NULL counts
+/// (counts[q] = the spans found, duplicates included); else the spans go to staging + raw_index[q], each once and in order, the
+/// rest of the segment is filled with records that name the string, and counts[q] = the spans kept.  store: 2 * max_len a lane.
+template <typename index_type, typename string_set_type>
+__global__ void __launch_bounds__(128) mem_rank_split_kernel(const uint32 n, const index_type f_index, const index_type r_index, const string_set_type string_set,
+                                                             const uint32 min_intv, const uint32 max_intv, const uint32 min_span, const uint32 split_len, const uint32 split_width,
+                                                             uint4* store, const uint32 max_len, uint64* counts, const uint64* raw_index,
+                                                             MEMRange<typename index_type::index_type>* staging)
+{
+    typedef typename index_type::index_type      coord_type;
+    typedef typename string_set_type::string_type string_type;
+    typedef mem_lane_sink<coord_type>            sink_type;
+    const uint32 q = blockIdx.x * 128u + threadIdx.x;
+    if (q >= n) return;
+    const string_type s = string_set[q];
+    const uint32 len = uint32(length(s)) < max_len ? uint32(length(s)) : max_len;
+    uint4* my_store  = store + size_t(q) * 2u * max_len;
+    uint4* my_store2 = my_store + max_len;
+    sink_type sink = { raw_index ? staging + raw_index[q] : NULL, 0u, 0u, q };
+    mem_split_handler<string_type, index_type, sink_type, uint4*> handler(len, s, f_index, r_index, sink, my_store2, max_intv, min_span, split_len, split_width, NULL);
+    for (uint32 x = 0; x < len;)
+    {
+        const uint32 e = find_kmems(len, s, x, f_index, r_index, handler, min_intv, min_span, my_store);
+        x = e > x + 1u ? e : x + 1u;
+    }
+    if (raw_index)
+        for (uint32 k = sink.kept; k < sink.raw; ++k) sink.seg[k] = MEMRange<coord_type>(make_vector(coord_type(0u), coord_type(0u)), q, make_uint2(0u, 0u));
+    counts[q] = raw_index ? sink.kept : sink.raw;
+}
+/// one lane per staged slot: the first index[q + 1] - index[q] slots of string q's segment are its records
+template <typename coord_type>
+__global__ void __launch_bounds__(128) mem_compact_kernel(const uint32 n_raw, const MEMRange<coord_type>* staging, const uint64* raw_index, const uint64* index,
+                                                          MEMRange<coord_type>* out, uint64* sizes)
+{
+    const uint32 t = blockIdx.x * 128u + threadIdx.x;
+    if (t >= n_raw) return;
+    const MEMRange<coord_type> r = staging[t];
+    const uint32 q = r.string_id();
+    const uint64 first = index[q], pos = t - raw_index[q];
+    if (pos >= index[q + 1u] - first) return;
+    out[first + pos] = r; sizes[first + pos] = uint64(r.range_size());
+}
 template <typename index_type, typename mems_iterator>
 __global__ void __launch_bounds__(128) mem_locate_kernel(const uint64 begin, const uint32 n_hits, const index_type index, const uint64 n_ranges, const uint64* slots,
                                                          const MEMRange<typename index_type::index_type>* ranges, mems_iterator mems)
@@ -329,6 +494,8 @@ __global__ void __launch_bounds__(128) mem_locate_kernel(const uint64 begin, con
 ///                nvbio_hip_fm_mem_rank / nvbio_hip_fm_mem_locate run the gfx950 kernels;
 ///   * generic -- any other fm_index<> / string set: one lane per string runs find_kmems, twice (count, hipCUB scan, write),
 ///                one lane per hit runs upper_bound + locate().
+/// Both honour split_len / split_width: the tuned one through nvbio_hip_fm_mem_rank_split, the generic one with lanes that re-seed
+/// their candidates as they report them and keep each string's spans in order and once in a staging table.
 template <typename fm_index_type>
 struct MEMFilter<device_tag, fm_index_type>
 {
@@ -350,7 +517,8 @@ struct MEMFilter<device_tag, fm_index_type>
     /// returns the total number of MEM occurrences
     template <typename string_set_type>
     uint64 rank(const fm_index_type& f_index, const fm_index_type& r_index, const string_set_type& string_set,
-                const uint32 min_intv = 1u, const uint32 max_intv = uint32(-1), const uint32 min_span = 1u)
+                const uint32 min_intv = 1u, const uint32 max_intv = uint32(-1), const uint32 min_span = 1u,
+                const uint32 split_len = uint32(-1), const uint32 split_width = uint32(-1))
     {
         m_n_queries = string_set.size();
         m_f_index = f_index; m_r_index = r_index;
@@ -369,8 +537,42 @@ struct MEMFilter<device_tag, fm_index_type>
         if (max_len > 65535u) throw std::runtime_error("MEMFilter::rank: a pattern is longer than 65 535 symbols");
         if (max_len == 0u) { m_path = "none"; return 0; }
         typedef typename string_set_type::string_type string_type;
-        if (!rank_tuned(string_set, max_len, k, max_intv, min_span,
-                        std::integral_constant<bool, fmindex::production_layout<fm_index_type>::ok && nvbio::priv::packed_view<string_type>::ok>()))
+        const bool tuned = rank_tuned(string_set, max_len, k, max_intv, min_span, split_len, split_width,
+                                      std::integral_constant<bool, fmindex::production_layout<fm_index_type>::ok && nvbio::priv::packed_view<string_type>::ok>());
+        if (!tuned && split_len != uint32(-1))
+        {
+            // count every span, scan, stage each string's spans in order and once, count again, scan, move them to their places
+            uint4*  store     = reinterpret_cast<uint4*>(m_store.reserve(uint64(n) * 2u * max_len * sizeof(uint4)));
+            uint64* raw_index = m_raw_index.reserve(uint64(n) + 1u);
+            fmindex::check(hipMemsetAsync(raw_index, 0, sizeof(uint64), m_stream), "hipMemsetAsync");
+            hipLaunchKernelGGL((fmindex::mem_rank_split_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
+                               string_set, k, max_intv, min_span, split_len, split_width, store, max_len, raw_index + 1, (const uint64*)NULL, (rank_type*)NULL);
+            fmindex::check(hipGetLastError(), "mem_rank_split_kernel");
+            scan(raw_index + 1, n);
+            uint64 raw = 0, total = 0;
+            fmindex::check(hipMemcpyAsync(&raw, raw_index + n, sizeof(uint64), hipMemcpyDeviceToHost, m_stream), "hipMemcpyAsync");
+            fmindex::check(hipStreamSynchronize(m_stream), "hipStreamSynchronize");
+            if (raw > 0x7FFFFFFFull) throw std::runtime_error("MEMFilter::rank: more than 2^31 - 1 MEMs in one call");
+            if (raw)
+            {
+                rank_type* staging = m_staging.reserve(raw);
+                hipLaunchKernelGGL((fmindex::mem_rank_split_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
+                                   string_set, k, max_intv, min_span, split_len, split_width, store, max_len, index + 1, (const uint64*)raw_index, staging);
+                fmindex::check(hipGetLastError(), "mem_rank_split_kernel");
+                scan(index + 1, n);
+                fmindex::check(hipMemcpyAsync(&total, index + n, sizeof(uint64), hipMemcpyDeviceToHost, m_stream), "hipMemcpyAsync");
+                fmindex::check(hipStreamSynchronize(m_stream), "hipStreamSynchronize");
+                rank_type* ranges = m_mem_ranges.reserve(total);
+                uint64*    slots  = m_slots.reserve(total);
+                hipLaunchKernelGGL((fmindex::mem_compact_kernel<coord_type>), dim3((uint32(raw) + 127u) / 128u), dim3(128), 0, m_stream, uint32(raw),
+                                   (const rank_type*)staging, (const uint64*)raw_index, (const uint64*)index, ranges, slots);
+                fmindex::check(hipGetLastError(), "mem_compact_kernel");
+                scan(slots, uint32(total));
+            }
+            m_n_ranges = total;
+            m_path = "generic";
+        }
+        else if (!tuned)
         {
             uint4* store = reinterpret_cast<uint4*>(m_store.reserve(uint64(n) * max_len * sizeof(uint4)));
             hipLaunchKernelGGL((fmindex::mem_rank_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
@@ -440,12 +642,13 @@ private:
         fmindex::check(hipcub::DeviceScan::InclusiveSum(temp, tb, values, values, int(n), m_stream), "hipcub::DeviceScan::InclusiveSum");
     }
     template <typename string_set_type>
-    bool rank_tuned(const string_set_type&, const uint32, const uint32, const uint32, const uint32, std::false_type) { return false; }
+    bool rank_tuned(const string_set_type&, const uint32, const uint32, const uint32, const uint32, const uint32, const uint32, std::false_type) { return false; }
     template <typename mems_iterator>
     bool locate_tuned(const uint64, const uint64, mems_iterator, std::false_type) { return false; }
 
     template <typename string_set_type>
-    bool rank_tuned(const string_set_type& string_set, const uint32 max_len, const uint32 min_intv, const uint32 max_intv, const uint32 min_span, std::true_type)
+    bool rank_tuned(const string_set_type& string_set, const uint32 max_len, const uint32 min_intv, const uint32 max_intv, const uint32 min_span,
+                    const uint32 split_len, const uint32 split_width, std::true_type)
     {
 #if defined(NVBIO_HIP_COMPAT_FILTER_TUNED)
         typedef typename string_set_type::string_type string_type;
@@ -469,24 +672,28 @@ private:
         strings.words = reinterpret_cast<const uint32*>(uintptr_t(b[0]) * 4u); strings.n_words = b[1] - b[0];
         strings.bits = view::BITS; strings.big_endian = view::BE ? 1u : 0u;
         strings.begin = begin; strings.length = len; strings.fixed_length = 0; strings._pad = 0;
-        const uint64 tb = nvbio_hip_fm_mem_temp_bytes(n, max_len);
-        uint8* temp = m_store.reserve(tb + 16u);
-        uint64 capacity = uint64(n) * max_len < 8ull * n + 1024u ? uint64(n) * max_len : 8ull * n + 1024u, found = 0;
+        const bool split = split_len != uint32(-1);          // re-seeding: its own entry, whose scratch grows with the capacity
+        uint64 capacity = split ? 16ull * n + 1024u : (uint64(n) * max_len < 8ull * n + 1024u ? uint64(n) * max_len : 8ull * n + 1024u), found = 0;
         for (int attempt = 0; attempt < 2; ++attempt)      // at most one retry, with the number the library found
         {
+            const uint64 tb = split ? nvbio_hip_fm_mem_split_temp_bytes(n, max_len, capacity) : nvbio_hip_fm_mem_temp_bytes(n, max_len);
+            uint8* temp = m_store.reserve(tb + 16u);
             rank_type* ranges = m_mem_ranges.reserve(capacity);
             uint64*    slots  = m_slots.reserve(capacity);
-            const int err = nvbio_hip_fm_mem_rank(&m_f_fmi, &m_r_fmi, &strings, n, max_len, min_intv, max_intv, min_span, reinterpret_cast<uint32*>(ranges), capacity,
-                                                  m_index.ptr, slots, &found, temp, tb, m_stream);
+            const int err = split ?
+                nvbio_hip_fm_mem_rank_split(&m_f_fmi, &m_r_fmi, &strings, n, max_len, min_intv, max_intv, min_span, split_len, split_width, reinterpret_cast<uint32*>(ranges), capacity,
+                                            m_index.ptr, slots, &found, temp, tb, m_stream) :
+                nvbio_hip_fm_mem_rank(&m_f_fmi, &m_r_fmi, &strings, n, max_len, min_intv, max_intv, min_span, reinterpret_cast<uint32*>(ranges), capacity,
+                                      m_index.ptr, slots, &found, temp, tb, m_stream);
             if (err == 801) return false;
-            if (err != NVBIO_HIP_ERROR_CAPACITY || attempt == 1) { fmindex::check(err, "nvbio_hip_fm_mem_rank"); break; }
+            if (err != NVBIO_HIP_ERROR_CAPACITY || attempt == 1) { fmindex::check(err, split ? "nvbio_hip_fm_mem_rank_split" : "nvbio_hip_fm_mem_rank"); break; }
             capacity = found;
         }
         m_n_ranges = found;
         m_tuned = true; m_path = "tuned";
         return true;
 #else
-        (void)string_set; (void)max_len; (void)min_intv; (void)max_intv; (void)min_span; return false;
+        (void)string_set; (void)max_len; (void)min_intv; (void)max_intv; (void)min_span; (void)split_len; (void)split_width; return false;
 #endif
     }
     template <typename mems_iterator>
@@ -514,7 +721,8 @@ public:
     uint64                            m_n_occurrences, m_n_ranges;
 private:
     fmindex::device_array<rank_type>  m_mem_ranges;
-    fmindex::device_array<uint64>     m_slots, m_index;
+    fmindex::device_array<rank_type>  m_staging;
+    fmindex::device_array<uint64>     m_slots, m_index, m_raw_index;
     fmindex::device_array<uint8>      m_temp, m_jobs, m_store;
     const char*                       m_path;
     hipStream_t                       m_stream;

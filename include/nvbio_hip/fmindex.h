@@ -214,9 +214,13 @@ struct MEMFilter<device_tag, fm_index_type>
 
     /// find and rank the MEMs of all strings; returns the total number of occurrences.  Room is kept for eight MEMs a string; when the
     /// library finds more, the call is repeated once with its count.  (The longest string, which the entry wants, is read from the set.)
+    /// split_len / split_width re-seed as BWA-MEM does: a MEM at least split_len long with at most split_width
+    /// occurrences stays, the (occurrences + 1)-SMEMs over its midpoint are added, and a string's MEMs are ordered by begin, then end.
+    /// The default split_len switches that off; any other runs nvbio_hip_fm_mem_rank_split, with room for sixteen a string at first.
     template <typename string_set_type>
     uint64 rank(const fm_index_type& f_index, const fm_index_type& r_index, const string_set_type& string_set,
-                const uint32 min_intv = 1u, const uint32 max_intv = uint32(-1), const uint32 min_span = 1u)
+                const uint32 min_intv = 1u, const uint32 max_intv = uint32(-1), const uint32 min_span = 1u,
+                const uint32 split_len = uint32(-1), const uint32 split_width = uint32(-1))
     {
         m_n_queries = string_set.size();
         uint32 max_pattern_len = 0;
@@ -232,17 +236,23 @@ struct MEMFilter<device_tag, fm_index_type>
         }
         m_f_index = f_index; m_r_index = r_index;
         m_index.resize(uint64(m_n_queries) + 1u);
-        const uint64 tb = nvbio_hip_fm_mem_temp_bytes(m_n_queries, max_pattern_len);
-        if (d_temp_storage.size() < tb) d_temp_storage.resize(tb);
+        const bool split = split_len != uint32(-1);
         const nvbio_hip_string_set s = string_set.abi();
-        uint64 capacity = std::min<uint64>(uint64(m_n_queries) * max_pattern_len, 8ull * m_n_queries + 1024u), found = 0;
+        uint64 capacity = split ? 16ull * m_n_queries + 1024u : std::min<uint64>(uint64(m_n_queries) * max_pattern_len, 8ull * m_n_queries + 1024u), found = 0;
         for (int attempt = 0; attempt < 2; ++attempt)
         {
+            // the split entry's scratch grows with the capacity
+            const uint64 tb = split ? nvbio_hip_fm_mem_split_temp_bytes(m_n_queries, max_pattern_len, capacity) : nvbio_hip_fm_mem_temp_bytes(m_n_queries, max_pattern_len);
+            if (d_temp_storage.size() < tb) d_temp_storage.resize(tb);
             m_mem_ranges.resize(capacity); m_slots.resize(capacity);
-            const int err = nvbio_hip_fm_mem_rank(&m_f_index.m, &m_r_index.m, &s, m_n_queries, max_pattern_len, min_intv, max_intv, min_span,
-                                                  reinterpret_cast<uint32*>(m_mem_ranges.data()), capacity, m_index.data(), m_slots.data(), &found,
-                                                  d_temp_storage.data(), d_temp_storage.size(), nullptr);
-            if (err != NVBIO_HIP_ERROR_CAPACITY || attempt == 1) { hip_check(err, "nvbio_hip_fm_mem_rank"); break; }
+            const int err = split ?
+                nvbio_hip_fm_mem_rank_split(&m_f_index.m, &m_r_index.m, &s, m_n_queries, max_pattern_len, min_intv, max_intv, min_span, split_len, split_width,
+                                            reinterpret_cast<uint32*>(m_mem_ranges.data()), capacity, m_index.data(), m_slots.data(), &found,
+                                            d_temp_storage.data(), d_temp_storage.size(), nullptr) :
+                nvbio_hip_fm_mem_rank(&m_f_index.m, &m_r_index.m, &s, m_n_queries, max_pattern_len, min_intv, max_intv, min_span,
+                                      reinterpret_cast<uint32*>(m_mem_ranges.data()), capacity, m_index.data(), m_slots.data(), &found,
+                                      d_temp_storage.data(), d_temp_storage.size(), nullptr);
+            if (err != NVBIO_HIP_ERROR_CAPACITY || attempt == 1) { hip_check(err, split ? "nvbio_hip_fm_mem_rank_split" : "nvbio_hip_fm_mem_rank"); break; }
             capacity = found;
         }
         m_n_ranges = found;

@@ -30,6 +30,7 @@ SYMBOLS = [
     "nvbio_hip_fm_filter_temp_bytes", "nvbio_hip_fm_filter_rank", "nvbio_hip_fm_filter_locate",
     "nvbio_hip_fm_extend", "nvbio_hip_fm_mem_temp_bytes", "nvbio_hip_fm_mem_rank", "nvbio_hip_fm_mem_locate",
     "nvbio_hip_fm_extend_host", "nvbio_hip_fm_mem_rank_host", "nvbio_hip_fm_mem_locate_host",
+    "nvbio_hip_fm_mem_split_temp_bytes", "nvbio_hip_fm_mem_rank_split", "nvbio_hip_fm_mem_rank_split_host",
     "nvbio_hip_build_bwt_occ_temp_bytes", "nvbio_hip_build_bwt_occ",
     "nvbio_hip_device_malloc", "nvbio_hip_device_free", "nvbio_hip_device_free_ordered", "nvbio_hip_device_free_after", "nvbio_hip_device_trim", "nvbio_hip_device_mem_info", "nvbio_hip_memcpy", "nvbio_hip_memset",
     "nvbio_hip_stream_synchronize", "nvbio_hip_stream_query", "nvbio_hip_host_malloc", "nvbio_hip_host_free", "nvbio_hip_stream_create", "nvbio_hip_stream_destroy",
@@ -219,6 +220,10 @@ def lib():
         L.nvbio_hip_fm_extend_host.argtypes = [i32, P(FMIndexStruct), P(FMIndexStruct), vp, vp, vp, u32, vp, vp, i32]
         L.nvbio_hip_fm_mem_rank_host.argtypes = [P(FMIndexStruct), P(FMIndexStruct), P(StringSetStruct), u32, u32, u32, u32, u32, vp, u64, vp, vp, P(u64), P(u64), i32]
         L.nvbio_hip_fm_mem_locate_host.argtypes = [P(FMIndexStruct), vp, vp, u64, u64, u64, vp, i32]
+        L.nvbio_hip_fm_mem_split_temp_bytes.argtypes = [u32, u32, u64]
+        L.nvbio_hip_fm_mem_split_temp_bytes.restype = u64
+        L.nvbio_hip_fm_mem_rank_split.argtypes = [P(FMIndexStruct), P(FMIndexStruct), P(StringSetStruct), u32, u32, u32, u32, u32, u32, u32, vp, u64, vp, vp, P(u64), vp, u64, vp]
+        L.nvbio_hip_fm_mem_rank_split_host.argtypes = [P(FMIndexStruct), P(FMIndexStruct), P(StringSetStruct), u32, u32, u32, u32, u32, u32, u32, vp, u64, vp, vp, P(u64), P(u64), i32]
         L.nvbio_hip_build_bwt_occ_temp_bytes.argtypes = [u32]
         L.nvbio_hip_build_bwt_occ_temp_bytes.restype = u64
         L.nvbio_hip_build_bwt_occ.argtypes = [u32, vp, vp, vp, vp, u64, vp]

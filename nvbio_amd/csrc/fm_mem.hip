@@ -37,6 +37,63 @@ __device__ __forceinline__ uint32_t pattern_symbol(const Stream& s, const uint64
     return uint32_t(pc.grp >> (4u * (i & 15u))) & 15u;
 }
 
+// one group of the walk: the k-SMEMs (k = min_intv) that cover symbol x go to report(range, begin, end), begin ascending; returns the
+// next x.  `st` holds the kept ranges: entry j, word w at st[(j * 3 + w) * 64].
+template <typename Report>
+__device__ __forceinline__ uint32_t mem_group(const Fmi& f, const Fmi& r, const StringSet& strings, const uint64_t pbegin, PatternCursor& pc,
+                                              const uint32_t len, const uint32_t x, const uint32_t min_intv, uint32_t* const st, Report&& report)
+{
+    // ---- right extension from x
+    uint32_t m = 0, i;
+    {
+        uint2 fr = make_uint2(0u, f.length), rr = make_uint2(0u, r.length);
+        for (i = x; i < len; ++i)
+        {
+            const uint32_t c = pattern_symbol(strings.s, pbegin, pc, i);
+            if (c > 3u) break;
+            uint2 nf = fr, nr = rr;
+            fm_extend_forward(r, nf, nr, c);
+            const uint32_t size = nf.y - nf.x + 1u;
+            if (size < min_intv) break;
+            if (i > x && size != fr.y - fr.x + 1u)
+            {
+                st[(m * 3u + 0u) * 64u] = fr.x; st[(m * 3u + 1u) * 64u] = fr.y; st[(m * 3u + 2u) * 64u] = i;
+                ++m;
+            }
+            fr = nf; rr = nr;
+        }
+        if (i > x)
+        {
+            st[(m * 3u + 0u) * 64u] = fr.x; st[(m * 3u + 1u) * 64u] = fr.y; st[(m * 3u + 2u) * 64u] = i;
+            ++m;
+        }
+    }
+    // ---- left extension of each kept range, shortest first; a span is held until the next one's begin is known
+    bool held = false;
+    uint2 hg = make_uint2(0u, 0u);
+    uint32_t hb = 0, he = 0;
+    for (uint32_t j = 0; j < m; ++j)
+    {
+        uint2 g = make_uint2(st[(j * 3u + 0u) * 64u], st[(j * 3u + 1u) * 64u]);
+        const uint32_t e = st[(j * 3u + 2u) * 64u];
+        int32_t l;
+        for (l = int32_t(x) - 1; l >= 0; --l)
+        {
+            const uint32_t c = pattern_symbol(strings.s, pbegin, pc, uint32_t(l));
+            if (c > 3u) break;
+            const uint2 k = fm_rank2(f, g.x - 1u, g.y, c);
+            const uint2 ng = make_uint2(f.L2[c] + k.x + 1u, f.L2[c] + k.y);
+            if (ng.y - ng.x + 1u < min_intv) break;
+            g = ng;
+        }
+        const uint32_t b = uint32_t(l + 1);
+        if (held && hb < b) report(hg, hb, he);
+        held = true; hg = g; hb = b; he = e;
+    }
+    if (held) report(hg, hb, he);
+    return (m != 0u && i > x + 1u) ? i : x + 1u;
+}
+
 template <bool EMIT>
 __global__ void __launch_bounds__(256)
 fm_mem_kernel(const Fmi f, const Fmi r, const StringSet strings, const uint32_t n, const uint32_t max_len,
@@ -71,60 +128,102 @@ fm_mem_kernel(const Fmi f, const Fmi r, const StringSet strings, const uint32_t 
             ++count;
         };
 
-        for (uint32_t x = 0; x < len;)
-        {
-            // ---- right extension from x
-            uint32_t m = 0, i;
-            {
-                uint2 fr = make_uint2(0u, f.length), rr = make_uint2(0u, r.length);
-                for (i = x; i < len; ++i)
-                {
-                    const uint32_t c = pattern_symbol(strings.s, pbegin, pc, i);
-                    if (c > 3u) break;
-                    uint2 nf = fr, nr = rr;
-                    fm_extend_forward(r, nf, nr, c);
-                    const uint32_t size = nf.y - nf.x + 1u;
-                    if (size < min_intv) break;
-                    if (i > x && size != fr.y - fr.x + 1u)
-                    {
-                        st[(m * 3u + 0u) * 64u] = fr.x; st[(m * 3u + 1u) * 64u] = fr.y; st[(m * 3u + 2u) * 64u] = i;
-                        ++m;
-                    }
-                    fr = nf; rr = nr;
-                }
-                if (i > x)
-                {
-                    st[(m * 3u + 0u) * 64u] = fr.x; st[(m * 3u + 1u) * 64u] = fr.y; st[(m * 3u + 2u) * 64u] = i;
-                    ++m;
-                }
-            }
-            // ---- left extension of each kept range, shortest first; a span is held until the next one's begin is known
-            bool held = false;
-            uint2 hg = make_uint2(0u, 0u);
-            uint32_t hb = 0, he = 0;
-            for (uint32_t j = 0; j < m; ++j)
-            {
-                uint2 g = make_uint2(st[(j * 3u + 0u) * 64u], st[(j * 3u + 1u) * 64u]);
-                const uint32_t e = st[(j * 3u + 2u) * 64u];
-                int32_t l;
-                for (l = int32_t(x) - 1; l >= 0; --l)
-                {
-                    const uint32_t c = pattern_symbol(strings.s, pbegin, pc, uint32_t(l));
-                    if (c > 3u) break;
-                    const uint2 k = fm_rank2(f, g.x - 1u, g.y, c);
-                    const uint2 ng = make_uint2(f.L2[c] + k.x + 1u, f.L2[c] + k.y);
-                    if (ng.y - ng.x + 1u < min_intv) break;
-                    g = ng;
-                }
-                const uint32_t b = uint32_t(l + 1);
-                if (held && hb < b) report(hg, hb, he);
-                held = true; hg = g; hb = b; he = e;
-            }
-            if (held) report(hg, hb, he);
-            x = (m != 0u && i > x + 1u) ? i : x + 1u;
-        }
+        for (uint32_t x = 0; x < len;) x = mem_group(f, r, strings, pbegin, pc, len, x, min_intv, st, report);
         if (!EMIT) counts[id] = count;
     }
+}
+
+// ---- re-seeding (split_len / split_width).  A reported MEM [b, e) that is at least split_len long and occurs at
+// most split_width times is a candidate; its re-seeds are the (occ + 1)-SMEMs that cover its midpoint, which is one group of the walk
+// above (mem_group): from x = (b + e) >> 1, right on the reverse index at the larger threshold, then left from x - 1 for every kept
+// range -- and no advance of x.
+//
+// Work shape: the persistent lane that ranks a string re-seeds its candidates the moment it reports them, so the re-seed's pattern
+// words and the first records of both walks are the ones the lane has just read.  The kept ranges of the re-seed need a second
+// lane-interleaved scratch area of max_len entries, because the base group's are still being consumed when a span is reported.
+// The union is made per lane inside the string's own segment of a staging table (caller's temp): every span is inserted at its
+// place by (begin, end), from the back -- the base MEMs arrive in order, a re-seed lands next to its candidate -- and a span that
+// is already there is dropped.  The first pass counts the spans before duplicates are removed; that count sizes the segments and
+// is what the entry reports when the capacity is too small.  A last kernel moves the kept records to their final places.
+
+// begin, then end, of a record's span word (begin | end << 16) as one ordered key
+__device__ __forceinline__ uint32_t span_key(const uint32_t w) { return (w << 16) | (w >> 16); }
+
+template <bool EMIT>
+__global__ void __launch_bounds__(256)
+fm_mem_split_kernel(const Fmi f, const Fmi r, const StringSet strings, const uint32_t n, const uint32_t max_len,
+                    const uint32_t min_intv, const uint32_t max_intv, const uint32_t min_span, const uint32_t split_len, const uint32_t split_width,
+                    uint32_t* __restrict__ store, uint64_t* __restrict__ raw_counts, const uint64_t* __restrict__ raw_index,
+                    uint4* __restrict__ staging, uint64_t* __restrict__ kept_counts, uint32_t* __restrict__ too_long)
+{
+    const uint32_t tid  = blockIdx.x * 256u + threadIdx.x;
+    uint32_t* const st  = store + size_t(tid >> 6) * max_len * 384u + (tid & 63u);        // the base group's entries, then the re-seed's
+    uint32_t* const st2 = st + size_t(max_len) * 192u;
+    for (uint64_t id = tid; id < n; id += uint64_t(gridDim.x) * 256u)
+    {
+        const uint64_t pbegin = strings.begin[id];
+        uint32_t len = strings.length ? strings.length[id] : strings.fixed_length;
+        if (len > max_len)                             // refused by the entry; the store has room for max_len entries
+        {
+            if (!EMIT) *too_long = 1u;
+            len = max_len;
+        }
+        uint4* const seg = EMIT ? staging + raw_index[id] : nullptr;       // room for every span counted by the first pass
+        uint32_t raw = 0, kept = 0;
+        PatternCursor pc; pc.g0 = 0xFFFFFFFFu; pc.grp = 0;
+
+        auto emit = [&](const uint2 g, const uint32_t b, const uint32_t e)
+        {
+            ++raw;
+            if (!EMIT) return;
+            const uint32_t w = b | (e << 16), key = span_key(w);
+            uint32_t p = kept;
+            for (; p > 0u; --p)
+            {
+                const uint32_t other = span_key(seg[p - 1u].w);
+                if (other == key) return;              // found before, by the base walk or through another candidate
+                if (other < key) break;
+            }
+            for (uint32_t q = kept; q > p; --q) seg[q] = seg[q - 1u];
+            seg[p] = make_uint4(g.x, g.y, uint32_t(id), w);
+            ++kept;
+        };
+        auto reseed = [&](const uint2 g, const uint32_t b, const uint32_t e)
+        {
+            if (e - b < min_span || g.y - g.x + 1u > max_intv) return;
+            emit(g, b, e);
+        };
+        auto base = [&](const uint2 g, const uint32_t b, const uint32_t e)
+        {
+            const uint32_t occ = g.y - g.x + 1u;
+            if (e - b < min_span || occ > max_intv) return;
+            emit(g, b, e);
+            if (e - b < split_len || occ > split_width) return;
+            const uint32_t k = occ == 0xFFFFFFFFu ? occ : occ + 1u;       // cannot wrap
+            (void)mem_group(f, r, strings, pbegin, pc, len, (b + e) >> 1, k, st2, reseed);
+        };
+        for (uint32_t x = 0; x < len;) x = mem_group(f, r, strings, pbegin, pc, len, x, min_intv, st, base);
+
+        if (!EMIT) raw_counts[id] = raw;
+        else
+        {
+            for (uint32_t q = kept; q < raw; ++q) seg[q] = make_uint4(0u, 0u, uint32_t(id), 0u);      // the compaction reads every slot's string
+            kept_counts[id] = kept;
+        }
+    }
+}
+
+// one thread per staged slot: the first out_index[id + 1] - out_index[id] slots of string id's segment are its records
+__global__ void __launch_bounds__(256)
+fm_mem_compact_kernel(const uint4* __restrict__ staging, const uint64_t* __restrict__ raw_index, const uint64_t* __restrict__ out_index,
+                      const uint64_t n_raw, uint4* __restrict__ out, uint64_t* __restrict__ sizes)
+{
+    const uint64_t t = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (t >= n_raw) return;
+    const uint4 rec = staging[t];
+    const uint64_t first = out_index[rec.z], pos = t - raw_index[rec.z];
+    if (pos >= out_index[rec.z + 1u] - first) return;
+    out[first + pos] = rec; sizes[first + pos] = rec.y - rec.x + 1u;
 }
 
 __global__ void __launch_bounds__(256)
@@ -168,6 +267,15 @@ static inline uint64_t mem_scan_bytes(uint32_t n, uint32_t max_len)
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan, (const uint64_t*)nullptr, (uint64_t*)nullptr, int(most));      // size query only
     return mem_align256(scan) + 256u;
 }
+// the split entry scans n counts and at most `capacity` sizes, and stages at most `capacity` records (never more than 2^31 - 1)
+static inline uint64_t mem_split_staged(uint64_t capacity) { return std::min<uint64_t>(capacity, 0x7FFFFFFFull); }
+static inline uint64_t mem_split_scan_bytes(uint32_t n, uint64_t capacity)
+{
+    size_t scan = 0;
+    (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan, (const uint64_t*)nullptr, (uint64_t*)nullptr, int(std::max<uint64_t>(mem_split_staged(capacity), n)));
+    return mem_align256(scan) + 256u;
+}
+static inline uint64_t mem_split_index_bytes(uint32_t n) { return mem_align256((uint64_t(n) + 1u) * 8u); }
 
 } // namespace nvb
 
@@ -255,6 +363,79 @@ NVB_API int nvbio_hip_fm_mem_rank(const nvbio_hip_fmindex* f_fmi, const nvbio_hi
         if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, out_slots, out_slots, int(stored), s)) return e;
     }
     return total > capacity ? NVBIO_HIP_ERROR_CAPACITY : hipSuccess;
+}
+
+NVB_API uint64_t nvbio_hip_fm_mem_split_temp_bytes(uint32_t n, uint32_t max_pattern_len, uint64_t capacity)
+{
+    if (n == 0 || max_pattern_len == 0 || max_pattern_len > 65535u || n >= 0x80000000u) return 256u;
+    const uint64_t split = 2u * mem_store_bytes(n, max_pattern_len) + mem_counts_bytes(n) + mem_split_index_bytes(n) +
+                           mem_split_scan_bytes(n, capacity) + mem_align256(mem_split_staged(capacity) * 16u);
+    return std::max<uint64_t>(split, nvbio_hip_fm_mem_temp_bytes(n, max_pattern_len));        // the no-split sentinel runs the plain entry
+}
+
+NVB_API int nvbio_hip_fm_mem_rank_split(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                                        uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                                        uint32_t split_len, uint32_t split_width,
+                                        uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                                        void* temp, uint64_t temp_bytes, void* stream)
+{
+    if (split_len == 0xFFFFFFFFu)                      // no re-seeding: the plain entry, word for word
+        return nvbio_hip_fm_mem_rank(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, max_intv, min_span, out_ranges, capacity, out_index, out_slots,
+                                     out_n_ranges, temp, temp_bytes, stream);
+    if (int e = check_bidir(f_fmi, r_fmi)) return e;
+    if (!out_index || !out_n_ranges || min_intv == 0u) return hipErrorInvalidValue;
+    if (n >= 0x80000000u || max_pattern_len > 65535u) return hipErrorInvalidValue;
+    if (capacity != 0u && (!out_ranges || !out_slots)) return hipErrorInvalidValue;
+    hipStream_t s = to_stream(stream);
+    *out_n_ranges = 0;
+    if (n == 0 || max_pattern_len == 0) return hipMemsetAsync(out_index, 0, (uint64_t(n) + 1u) * 8u, s);
+    if (!strings || !strings->words || !strings->begin || strings->n_words == 0) return hipErrorInvalidValue;
+    if (!(strings->bits == 2 || strings->bits == 4)) return hipErrorNotSupported;
+    if (!strings->length && strings->fixed_length > max_pattern_len) return hipErrorInvalidValue;
+    if (!temp || temp_bytes < nvbio_hip_fm_mem_split_temp_bytes(n, max_pattern_len, capacity)) return hipErrorInvalidValue;
+
+    uint8_t*  p         = reinterpret_cast<uint8_t*>(temp);
+    uint32_t* store     = reinterpret_cast<uint32_t*>(p);               p += 2u * mem_store_bytes(n, max_pattern_len);
+    uint64_t* counts    = reinterpret_cast<uint64_t*>(p);               p += mem_counts_bytes(n);       // before, then after, duplicates go
+    uint32_t* too_long  = reinterpret_cast<uint32_t*>(p - 256);
+    uint64_t* raw_index = reinterpret_cast<uint64_t*>(p);               p += mem_split_index_bytes(n);
+    void*     scan      = p;                                            p += mem_split_scan_bytes(n, capacity);
+    size_t scan_bytes   = size_t(mem_split_scan_bytes(n, capacity));
+    uint4*    staging   = reinterpret_cast<uint4*>(p);
+    const dim3 grid(mem_blocks(n)), block(256);
+    const Fmi f = make_fmi(f_fmi), r = make_fmi(r_fmi);
+    const StringSet set = make_string_set(strings);
+
+    if (hipError_t e = hipMemsetAsync(out_index, 0, 8u, s)) return e;
+    if (hipError_t e = hipMemsetAsync(raw_index, 0, 8u, s)) return e;
+    if (hipError_t e = hipMemsetAsync(too_long, 0, 4u, s)) return e;
+    g_last_kernel = "fm_mem_split_kernel";
+    hipLaunchKernelGGL(fm_mem_split_kernel<false>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span, split_len, split_width,
+                       store, counts, (const uint64_t*)nullptr, (uint4*)nullptr, (uint64_t*)nullptr, too_long);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, counts, raw_index + 1, int(n), s)) return e;
+    uint64_t raw = 0, total = 0;
+    uint32_t refused = 0;
+    if (hipError_t e = hipMemcpyAsync(&raw, raw_index + n, 8u, hipMemcpyDeviceToHost, s)) return e;
+    if (hipError_t e = hipMemcpyAsync(&refused, too_long, 4u, hipMemcpyDeviceToHost, s)) return e;
+    if (hipError_t e = hipStreamSynchronize(s)) return e;
+    if (refused) return hipErrorInvalidValue;                          // a string longer than max_pattern_len
+    if (raw > capacity) { *out_n_ranges = raw; return NVBIO_HIP_ERROR_CAPACITY; }       // the staging table has room for `capacity` spans
+    if (raw > 0x7FFFFFFFull) return hipErrorInvalidValue;              // the scans count in 31 bits
+    if (raw == 0) return hipMemsetAsync(out_index, 0, (uint64_t(n) + 1u) * 8u, s);
+
+    hipLaunchKernelGGL(fm_mem_split_kernel<true>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span, split_len, split_width,
+                       store, (uint64_t*)nullptr, raw_index, staging, counts, (uint32_t*)nullptr);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, counts, out_index + 1, int(n), s)) return e;
+    hipLaunchKernelGGL(fm_mem_compact_kernel, dim3(uint32_t((raw + 255u) / 256u)), block, 0, s, staging, raw_index, out_index, raw,
+                       reinterpret_cast<uint4*>(out_ranges), out_slots);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = hipMemcpyAsync(&total, out_index + n, 8u, hipMemcpyDeviceToHost, s)) return e;
+    if (hipError_t e = hipStreamSynchronize(s)) return e;
+    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, out_slots, out_slots, int(total), s)) return e;
+    *out_n_ranges = total;
+    return hipSuccess;
 }
 
 NVB_API int nvbio_hip_fm_mem_locate(const nvbio_hip_fmindex* f_fmi, const uint32_t* ranges, const uint64_t* slots, uint64_t n_ranges,

@@ -348,6 +348,60 @@ NVB_API int nvbio_hip_fm_mem_rank_host(const nvbio_hip_fmindex* f_fmi, const nvb
     return out_index[n] > capacity ? NVBIO_HIP_ERROR_CAPACITY : int(hipSuccess);
 }
 
+NVB_API int nvbio_hip_fm_mem_rank_split_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                                             uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                                             uint32_t split_len, uint32_t split_width,
+                                             uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                                             uint64_t* out_records, int32_t n_threads)
+{
+    if (split_len == 0xFFFFFFFFu)                      // no re-seeding: the plain twin, word for word
+        return nvbio_hip_fm_mem_rank_host(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, max_intv, min_span, out_ranges, capacity, out_index, out_slots,
+                                          out_n_ranges, out_records, n_threads);
+    if (!f_fmi || !r_fmi || !f_fmi->bwt_occ || !r_fmi->bwt_occ || f_fmi->length != r_fmi->length) return hipErrorInvalidValue;
+    if (!out_index || !out_n_ranges || min_intv == 0u) return hipErrorInvalidValue;
+    if (n >= 0x80000000u || max_pattern_len > 65535u) return hipErrorInvalidValue;
+    if (capacity != 0u && (!out_ranges || !out_slots)) return hipErrorInvalidValue;
+    *out_n_ranges = 0;
+    if (out_records) *out_records = 0;
+    out_index[0] = 0;
+    if (n == 0 || max_pattern_len == 0) { for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = 0; return hipSuccess; }
+    if (!strings || !strings->words || !strings->begin || strings->n_words == 0) return hipErrorInvalidValue;
+    if (!(strings->bits == 2 || strings->bits == 4)) return hipErrorNotSupported;
+    if (!strings->length && strings->fixed_length > max_pattern_len) return hipErrorInvalidValue;
+    if (strings->length) for (uint32 i = 0; i < n; ++i) if (strings->length[i] > max_pattern_len) return hipErrorInvalidValue;
+    const fmi_t f = host_index(f_fmi), r = host_index(r_fmi);
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#endif
+    std::vector< std::vector< MEMRange<uint32> > > found(n);
+    uint64 records = 0, raw = 0;
+    #pragma omp parallel num_threads(threads) reduction(+ : records, raw)
+    {
+        std::vector<uint4> store, store2;
+        #pragma omp for schedule(dynamic, 256)
+        for (int64 i = 0; i < int64(n); ++i)
+        {
+            const RtString s = string_of(strings, uint32(i));
+            const uint32 len = s.len < max_pattern_len ? s.len : max_pattern_len;
+            raw += fmindex::string_mems_split(s, len, uint32(i), f, r, min_intv, max_intv, min_span, split_len, split_width, found[i], store, store2, &records);
+        }
+    }
+    if (out_records) *out_records = records;
+    if (raw > capacity) { *out_n_ranges = raw; return NVBIO_HIP_ERROR_CAPACITY; }       // the device entry stages every span found: the same rule
+    for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = out_index[i] + found[i].size();
+    uint64 sum = 0;
+    for (uint32 i = 0; i < n; ++i)
+        for (size_t k = 0; k < found[i].size(); ++k)
+        {
+            const uint64 at = out_index[i] + k;
+            const uint4 v = found[i][k].coords;
+            out_ranges[4 * at] = v.x; out_ranges[4 * at + 1] = v.y; out_ranges[4 * at + 2] = v.z; out_ranges[4 * at + 3] = v.w;
+            sum += uint64(found[i][k].range_size()); out_slots[at] = sum;
+        }
+    *out_n_ranges = out_index[n];
+    return hipSuccess;
+}
+
 NVB_API int nvbio_hip_fm_mem_locate_host(const nvbio_hip_fmindex* f_fmi, const uint32_t* ranges, const uint64_t* slots, uint64_t n_ranges,
                                          uint64_t begin, uint64_t end, uint32_t* out_hits, int32_t n_threads)
 {

@@ -295,10 +295,16 @@ class MEMFilter:
         self.f_index = None
         self.r_index = None
 
-    def rank(self, f_index, r_index, string_set, min_intv=1, max_intv=0xFFFFFFFF, min_span=1, capacity=None):
+    def rank(self, f_index, r_index, string_set, min_intv=1, max_intv=0xFFFFFFFF, min_span=1, capacity=None,
+             split_len=0xFFFFFFFF, split_width=0xFFFFFFFF):
         """-> the total number of MEM occurrences.  `capacity`: room for the ranges, by default eight a string (never more than
         the sum of the string lengths, which cannot be too small); when the library finds more, the call is repeated once with the
-        number it found."""
+        number it found.
+
+        split_len / split_width re-seed (MEMFilter::rank's last two arguments, DESIGN.md 3.12): a MEM at least split_len long that
+        occurs at most split_width times keeps its place, and the (occurrences + 1)-SMEMs over its midpoint are added; a string's
+        MEMs are then ordered by begin, then end.  The default split_len switches it off and takes nvbio_hip_fm_mem_rank; any other
+        takes nvbio_hip_fm_mem_rank_split, whose output the sum of the lengths does not bound (default room: sixteen a string)."""
         n = len(string_set)
         dev = string_set.words.device
         self.f_index, self.r_index, self.n_queries = f_index, r_index, n
@@ -307,25 +313,35 @@ class MEMFilter:
             total_len = int(string_set.length.sum().item()) if n else 0
         else:
             max_len, total_len = string_set.fixed_length, n * string_set.fixed_length
+        split = split_len != 0xFFFFFFFF
         if capacity is None:
-            capacity = min(total_len, 8 * n + 1024)
+            capacity = 16 * n + 1024 if split else min(total_len, 8 * n + 1024)
         L = lib()
-        tb = int(L.nvbio_hip_fm_mem_temp_bytes(n, max_len))
-        temp = torch.empty(tb, dtype=torch.uint8, device=dev)
         self.index = torch.empty(n + 1, dtype=torch.int64, device=dev)
         fs, rs, ss = f_index.struct(), r_index.struct(), string_set.struct()
         found = C.c_uint64(0)
         cap = int(capacity)
-        for _ in range(2):      # at most one retry, with the number the first call found
+        temp = None
+        for _ in range(2):      # at most one retry, with the number the first call reported
             self.ranges = torch.empty((cap, 4), dtype=torch.int32, device=dev)
             self.slots = torch.empty(cap, dtype=torch.int64, device=dev)
-            err = L.nvbio_hip_fm_mem_rank(C.byref(fs), C.byref(rs), C.byref(ss), n, max_len, min_intv, max_intv, min_span,
-                                          _vp(self.ranges), cap, _vp(self.index), _vp(self.slots), C.byref(found), _vp(temp), tb,
-                                          current_stream_ptr())
+            if split:           # its scratch grows with the capacity
+                tb = int(L.nvbio_hip_fm_mem_split_temp_bytes(n, max_len, cap))
+                temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+                err = L.nvbio_hip_fm_mem_rank_split(C.byref(fs), C.byref(rs), C.byref(ss), n, max_len, min_intv, max_intv, min_span,
+                                                    split_len, split_width, _vp(self.ranges), cap, _vp(self.index), _vp(self.slots),
+                                                    C.byref(found), _vp(temp), tb, current_stream_ptr())
+            else:
+                if temp is None:
+                    tb = int(L.nvbio_hip_fm_mem_temp_bytes(n, max_len))
+                    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+                err = L.nvbio_hip_fm_mem_rank(C.byref(fs), C.byref(rs), C.byref(ss), n, max_len, min_intv, max_intv, min_span,
+                                              _vp(self.ranges), cap, _vp(self.index), _vp(self.slots), C.byref(found), _vp(temp), tb,
+                                              current_stream_ptr())
             if err != ERROR_CAPACITY:
                 break
             cap = int(found.value)
-        check(err, "nvbio_hip_fm_mem_rank")
+        check(err, "nvbio_hip_fm_mem_rank_split" if split else "nvbio_hip_fm_mem_rank")
         k = int(found.value)
         self.ranges, self.slots = self.ranges[:k], self.slots[:k]
         self.n_occurrences = int(self.slots[k - 1].item()) if k else 0

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Times MEM seeding (nvbio_hip_fm_mem_rank / nvbio_amd.MEMFilter) and writes the figures to a file.
+"""Times MEM seeding (nvbio_hip_fm_mem_rank, nvbio_hip_fm_mem_rank_split / nvbio_amd.MEMFilter) and writes the figures to a file.
 
 Workload: --reads (1 M) reads of 150 bp sampled from a random genome of 2^--text-log2 (2^28) symbols with 2 % substitutions, 4-bit
 big-endian, against the forward index and the index of the reversed genome, both built on the device; min_intv 1, min_span 19,
@@ -9,7 +9,11 @@ around each; the median and the spread are reported as reads/s, with MEMs per re
 nvbio_hip_fm_rank over 2^24 random rows of the same index, one 32-byte record each.  The only other implementation is the `_host`
 twin on 16 threads: it is timed on the first --host-reads (100 k) reads of the same set (--host-reps (5) calls after a warm-up), whose
 ranks must equal the device's.
-Usage: python tools/mem_time.py [--out profiles/mem/mem_time.txt]"""
+With --split-len / --split-width (nvmem's are 28 and 10) the same run then times nvbio_hip_fm_mem_rank_split on the same reads and reports,
+next to the plain figures, the MEMs per read after re-seeding, the extra index records the re-seed walks read (the two host twins'
+counts on the first --host-reads reads) and the gather rate of that added work, extra records over extra time; the default output file
+is then profiles/mem/mem_split_time.txt.
+Usage: python tools/mem_time.py [--split-len 28 --split-width 10] [--out profiles/mem/mem_time.txt]"""
 import argparse
 import ctypes as C
 import os
@@ -57,8 +61,13 @@ def main():
     ap.add_argument("--host-reads", type=int, default=100_000)
     ap.add_argument("--host-threads", type=int, default=16)
     ap.add_argument("--host-reps", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mem", "mem_time.txt"))
+    ap.add_argument("--split-len", type=lambda v: int(v, 0), default=0xFFFFFFFF)
+    ap.add_argument("--split-width", type=lambda v: int(v, 0), default=0xFFFFFFFF)
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    split = a.split_len != 0xFFFFFFFF
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "mem", "mem_split_time.txt" if split else "mem_time.txt")
     dev = torch.device("cuda:0")
     n, ln, G = a.reads, 150, 1 << a.text_log2
     min_intv, max_intv, min_span = 1, 10000, 19
@@ -142,6 +151,38 @@ def main():
             a.host_threads, hn, a.host_reps, float(np.median(h_s)), min(h_s), max(h_s), hn / float(np.median(h_s)), reads_s / (hn / float(np.median(h_s)))),
         "  device ranks of those reads equal the host twin's: %s" % same,
     ]
+    if split:
+        # the same reads through the re-seeding entry: its own scratch, the same output arrays
+        tb_s = int(L.nvbio_hip_fm_mem_split_temp_bytes(n, ln, cap))
+        del temp
+        temp_s = torch.empty(tb_s, dtype=torch.uint8, device=dev)
+
+        def run_split():
+            nvb.check(L.nvbio_hip_fm_mem_rank_split(C.byref(fs), C.byref(rs), C.byref(ss), n, ln, min_intv, max_intv, min_span, a.split_len, a.split_width,
+                                                    vp(ranges), cap, vp(index), vp(slots), C.byref(found), vp(temp_s), tb_s, _lib.current_stream_ptr()),
+                      "nvbio_hip_fm_mem_rank_split")
+        ms_s = timed(run_split, a.reps)
+        n_mems_s = int(found.value)
+        s_found, s_records = C.c_uint64(0), C.c_uint64(0)
+        nvb.check(L.nvbio_hip_fm_mem_rank_split_host(C.byref(hfs), C.byref(hrs), C.byref(hss), hn, ln, min_intv, max_intv, min_span, a.split_len, a.split_width,
+                                                     h_ranges.ctypes.data, 16 * hn, h_index.ctypes.data, h_slots.ctypes.data, C.byref(s_found), C.byref(s_records),
+                                                     a.host_threads), "nvbio_hip_fm_mem_rank_split_host")
+        k_s = int(s_found.value)
+        same_s = bool((ranges[:k_s].cpu().numpy().view(np.uint32) == h_ranges[:k_s]).all()) and bool((index[:hn + 1].cpu().numpy().view(np.uint64) == h_index).all())
+        same = same and same_s
+        med_s = float(np.median(ms_s))
+        extra_rec = (s_records.value - h_records.value) / hn            # per read, one walk
+        extra_ms = med_s - med
+        added_rate = 2.0 * extra_rec * n / (extra_ms * 1e-3) if extra_ms > 0 else float("inf")
+        lines += [
+            "nvbio_hip_fm_mem_rank_split  split_len %d, split_width %d   %d calls, ms: median %.2f  (min %.2f .. max %.2f)   %.3g reads/s   split / plain = %.2f" % (
+                a.split_len, a.split_width, a.reps, med_s, min(ms_s), max(ms_s), n / (med_s * 1e-3), med_s / med),
+            "  MEMs per read %.2f (plain %.2f)   temp %.0f MB" % (n_mems_s / n, n_mems / n, tb_s / 1e6),
+            "  extra records gathered per read by the re-seed walks (host twins' counts, one walk) %.1f (plain %.1f); both passes walk: %.3g records in %.2f ms extra = %.3g records/s" % (
+                extra_rec, rec_per_read, 2.0 * extra_rec * n, extra_ms, added_rate),
+            "  gather rate of the added work / the plain entry's gather rate in this run = %.2f" % (added_rate / gather_rate),
+            "  device ranks of the first %d reads equal the split host twin's: %s" % (hn, same_s),
+        ]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     open(a.out, "w").write("\n".join(lines) + "\n")
     print("\n".join(lines))
