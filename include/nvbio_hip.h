@@ -1034,6 +1034,33 @@ uint64_t nvbio_hip_build_bwt_occ_temp_bytes(uint32_t n);
 int nvbio_hip_build_bwt_occ(uint32_t n, const uint32_t* bwt_words, uint32_t* out_bwt_occ, uint32_t* out_L2,
                             void* temp, uint64_t temp_bytes, void* stream);
 
+/* ---- Suffix sorting and BWT construction of one 2-bit text (nvbio/sufsort/sufsort.h: cuda::suffix_sort, cuda::bwt, cuda::find_primary
+ * for a plain string).
+ * words: the text, 2-bit packed in either PackedStream order (big_endian as in nvbio_hip_string_set), ceil(n / 16) words; bits must be 2;
+ * 1 <= n <= 0xFFFFFFFE.  sa_out: uint32[n + 1] in the convention of compat/nvbio/fmindex/bwt.h: SA[0] = n is the empty suffix, and a
+ * suffix that is a proper prefix of another sorts first.
+ * nvbio_hip_bwt also writes what an FM-index is built from: bwt_words_out = the BWT with the '$' row dropped (bwt[row] = T[SA[row] - 1]),
+ * big-endian 2-bit, 4 * ceil(n / 64) words, zero padded -- what nvbio_hip_build_bwt_occ takes; *primary_out (a HOST word) = the row whose
+ * suffix is 0; ssa_out (may be NULL) = uint32[ceil((n + 1) / sa_int)], ssa[k] = SA[k * sa_int], ssa[0] = 0xFFFFFFFF; sa_out (may be NULL)
+ * = the whole SA as above.
+ * temp: device scratch of the matching _temp_bytes(n) bytes (36 bytes a symbol, 40 for nvbio_hip_bwt, plus rocPRIM's); nothing is
+ * allocated inside.  Both entries wait for the stream once per sorting round -- the count of suffixes still unresolved has to reach the
+ * host to end the loop -- and have finished when they return.  Invalid arguments (a null pointer, bits != 2, n == 0, n above the
+ * maximum, too little temp) return hipErrorInvalidValue and launch nothing.
+ * nvbio_hip_suffix_sort_last_rounds: the sorting rounds of this thread's last call, and in out_unresolved[r] (up to `capacity`; may be
+ * NULL) the suffixes left unresolved after round r.
+ * The host twins take host pointers and a thread count, and return the same bytes. */
+uint64_t nvbio_hip_suffix_sort_temp_bytes(uint64_t n);
+int nvbio_hip_suffix_sort(const uint32_t* words, uint32_t bits, uint32_t big_endian, uint64_t n, uint32_t* sa_out,
+                          void* temp, uint64_t temp_bytes, void* stream);
+uint32_t nvbio_hip_suffix_sort_last_rounds(uint64_t* out_unresolved, uint32_t capacity);
+uint64_t nvbio_hip_bwt_temp_bytes(uint64_t n);
+int nvbio_hip_bwt(const uint32_t* words, uint32_t bits, uint32_t big_endian, uint64_t n, uint32_t sa_int, uint32_t* bwt_words_out,
+                  uint32_t* primary_out, uint32_t* ssa_out, uint32_t* sa_out, void* temp, uint64_t temp_bytes, void* stream);
+int nvbio_hip_suffix_sort_host(const uint32_t* words, uint32_t bits, uint32_t big_endian, uint64_t n, uint32_t* sa_out, int32_t n_threads);
+int nvbio_hip_bwt_host(const uint32_t* words, uint32_t bits, uint32_t big_endian, uint64_t n, uint32_t sa_int, uint32_t* bwt_words_out,
+                       uint32_t* primary_out, uint32_t* ssa_out, uint32_t* sa_out, int32_t n_threads);
+
 /* Device-memory helpers for host code that has no HIP headers (the C++ host layer in
  * include/nvbio_hip/ uses them where the reference uses thrust::device_vector).
  * kind: 1 = host->device, 2 = device->host, 3 = device->device. */

@@ -1,0 +1,233 @@
+// compat/nvbio/sufsort/sufsort.h -- the plain-string front door of the reference's suffix sorting module (nvbio/sufsort/sufsort.h):
+//
+//   BWTParams                                                   the construction parameters (kept for source compatibility; the sorter
+//                                                               here works in device memory only and reads none of them)
+//   cuda::find_primary(string_len, string)                      the row of suffix 0 among the string_len + 1 sorted suffixes
+//   cuda::suffix_sort(string_len, string, output, params)       output[0] = string_len (the empty suffix), output[1 .. string_len] the
+//                                                               suffixes in order: string_len + 1 entries (sufsort_inl.h:149-162)
+//   cuda::bwt(string_len, string, output, params) -> primary    string_len symbols: T[SA[row] - 1] over the rows but the primary, the
+//                                                               '$' removed and the symbols after it shifted back (sufsort_inl.h:239-265,
+//                                                               sufsort_utils.h:358-366, :412); the primary counts the empty suffix's row
+//
+// `string` is a device-side iterator over a 2-bit alphabet.  A PackedStream over a word pointer that starts on a word boundary goes to
+// nvbio_hip_suffix_sort / nvbio_hip_bwt (include/nvbio_hip.h) in place; any other 2-bit iterator is packed into
+// big-endian words first, then takes the same call.  Wider alphabets throw.  blockwise_suffix_sort, the string-set sorters and
+// large_bwt are not provided.  Needs a translation unit compiled by hipcc and linked with libnvbio_hip.
+#pragma once
+#include "../basic/types.h"
+#include "../basic/packedstream.h"
+#include "../basic/packed_view.h"
+#include "../basic/vector.h"
+#include "../../../../nvbio_hip.h"
+#include <hip/hip_runtime.h>
+#include <stdexcept>
+#include <string>
+
+namespace nvbio {
+
+/// BWT construction parameters (sufsort.h:92-107)
+struct BWTParams
+{
+    BWTParams() :
+        host_memory(8u * 1024u * 1024u * 1024llu),
+        device_memory(2u * 1024u * 1024u * 1024llu),
+        bucketing_bits(16u),
+        radix_slice(4u),
+        cpu_bucketing(0u) {}
+
+    uint64 host_memory;
+    uint64 device_memory;
+    uint32 bucketing_bits;
+    uint32 radix_slice;
+    uint32 cpu_bucketing;
+};
+
+namespace sufsort {
+
+inline void check(const int err, const char* what)
+{
+    if (err != 0) throw std::runtime_error(std::string("nvbio::cuda sufsort: ") + what + " failed with hipError " + std::to_string(err));
+}
+
+/// device scratch that lives for one call
+struct scratch
+{
+    explicit scratch(const uint64 bytes) : ptr(nullptr) { check(hipMalloc(&ptr, bytes ? bytes : 1u), "hipMalloc"); }
+    ~scratch() { if (ptr) (void)hipFree(ptr); }
+    scratch(const scratch&) = delete;
+    scratch& operator=(const scratch&) = delete;
+    template <typename T> T* as() const { return reinterpret_cast<T*>(ptr); }
+    void* ptr;
+};
+
+/// the position, in symbols from a word boundary, at which an iterator's first symbol lies when it is a PackedStream (0 otherwise):
+/// lanes that each own 16 symbols aligned to it own whole words
+template <typename It> struct word_phase { NVBIO_HOST_DEVICE static uint32 get(const It&) { return 0u; } };
+template <typename I, typename S, uint32 B, bool E, typename X>
+struct word_phase< PackedStream<I, S, B, E, X> > { NVBIO_HOST_DEVICE static uint32 get(const PackedStream<I, S, B, E, X>& s) { return uint32(uint64(s.index()) & 15u); } };
+
+/// word w of the big-endian 2-bit packing of string[0 .. n)
+template <typename string_type>
+__global__ void pack_kernel(const uint64 n, const string_type string, const uint64 n_words, uint32* words)
+{
+    const uint64 w = uint64(blockIdx.x) * 256u + threadIdx.x;
+    if (w >= n_words) return;
+    uint32 out = 0u;
+    for (uint32 q = 0; q < 16u; ++q)
+    {
+        const uint64 i = w * 16u + q;
+        if (i < n) out |= (uint32(string[i]) & 3u) << (30u - 2u * q);
+    }
+    words[w] = out;
+}
+
+/// output[i] = symbol i of big-endian 2-bit words; lane t owns the symbols whose position from the output's word boundary is in
+/// [16 t, 16 t + 16), so no two lanes write one word of a packed output
+template <typename output_iterator>
+__global__ void unpack_kernel(const uint64 n, const uint32* words, output_iterator output, const uint32 phase, const uint64 n_lanes)
+{
+    const uint64 t = uint64(blockIdx.x) * 256u + threadIdx.x;
+    if (t >= n_lanes) return;
+    for (uint32 q = 0; q < 16u; ++q)
+    {
+        const uint64 at = t * 16u + q;                   // from the word boundary
+        if (at < phase) continue;
+        const uint64 i = at - phase;
+        if (i < n) output[i] = uint8((words[i >> 4] >> (30u - 2u * uint32(i & 15u))) & 3u);
+    }
+}
+
+template <typename output_iterator>
+__global__ void copy_kernel(const uint64 n, const uint32* in, output_iterator output)
+{
+    const uint64 i = uint64(blockIdx.x) * 256u + threadIdx.x;
+    if (i < n) output[i] = in[i];
+}
+
+/// a 2-bit text as the C-ABI takes it: the caller's own words where the string is a word-aligned PackedStream over a word pointer,
+/// else a packed copy
+template <typename string_type>
+struct packed_text
+{
+    typedef nvbio::priv::packed_stream_where<string_type> where_type;
+
+    packed_text(const uint64 n, const string_type& string) : words(nullptr), big_endian(1u), copy(nullptr)
+    {
+        if (stream_traits<string_type>::SYMBOL_SIZE != 2u)
+            throw std::runtime_error("nvbio::cuda sufsort: only 2-bit alphabets are supported");
+        if (!in_place(n, string, std::integral_constant<bool, where_type::ok && where_type::BITS == 2u>()))
+        {
+            const uint64 n_words = (n + 15u) / 16u;
+            copy = new scratch(n_words * 4u);
+            hipLaunchKernelGGL((pack_kernel<string_type>), dim3(uint32((n_words + 255u) / 256u)), dim3(256), 0, 0, n, string, n_words, copy->template as<uint32>());
+            check(hipGetLastError(), "pack_kernel");
+            words = copy->template as<uint32>();
+        }
+    }
+    ~packed_text() { delete copy; }
+    packed_text(const packed_text&) = delete;
+    packed_text& operator=(const packed_text&) = delete;
+
+    bool in_place(const uint64, const string_type&, std::false_type) { return false; }
+    bool in_place(const uint64, const string_type& string, std::true_type)
+    {
+        uint64 word0; uint32 first;
+        where_type::where(string, word0, first);
+        if (first != 0u) return false;
+        words = reinterpret_cast<const uint32*>(uintptr_t(word0) * 4u);
+        big_endian = where_type::BE ? 1u : 0u;
+        return true;
+    }
+
+    const uint32* words;
+    uint32        big_endian;
+    scratch*      copy;
+};
+
+/// the caller's own memory when the output iterator walks plain 32-bit words, else NULL
+template <typename It, bool OK = nvbio::priv::plain_iterator<It>::ok> struct plain_words { static uint32* get(It) { return nullptr; } };
+template <typename It> struct plain_words<It, true>
+{
+    typedef nvbio::priv::plain_iterator<It> plain;
+    static uint32* get(It it) { return sizeof(typename plain::value_type) == 4u ? reinterpret_cast<uint32*>(plain::get(it)) : nullptr; }
+};
+
+inline void check_length(const uint64 n)
+{
+    if (n == 0u || n > 0xFFFFFFFEull) throw std::runtime_error("nvbio::cuda sufsort: the string must hold between 1 and 2^32 - 2 symbols");
+}
+
+} // namespace sufsort
+
+namespace cuda {
+
+/// Sort all the suffixes of a given string: string_len + 1 entries, the empty suffix first
+template <typename string_type, typename output_iterator>
+void suffix_sort(
+    const typename stream_traits<string_type>::index_type   string_len,
+    const string_type                                       string,
+    output_iterator                                         output,
+    BWTParams*                                              params)
+{
+    (void)params;
+    const uint64 n = string_len;
+    sufsort::check_length(n);
+    sufsort::packed_text<string_type> text(n, string);
+    const uint64 tb = nvbio_hip_suffix_sort_temp_bytes(n);
+    sufsort::scratch temp(tb);
+    if (uint32* direct = sufsort::plain_words<output_iterator>::get(output))
+    {
+        sufsort::check(nvbio_hip_suffix_sort(text.words, 2u, text.big_endian, n, direct, temp.ptr, tb, nullptr), "nvbio_hip_suffix_sort");
+        return;
+    }
+    sufsort::scratch sa((n + 1u) * 4u);
+    sufsort::check(nvbio_hip_suffix_sort(text.words, 2u, text.big_endian, n, sa.as<uint32>(), temp.ptr, tb, nullptr), "nvbio_hip_suffix_sort");
+    hipLaunchKernelGGL((sufsort::copy_kernel<output_iterator>), dim3(uint32((n + 256u) / 256u)), dim3(256), 0, 0, n + 1u, sa.as<uint32>(), output);
+    sufsort::check(hipGetLastError(), "copy_kernel");
+    sufsort::check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+}
+
+/// Compute the bwt of a device-side string: string_len symbols, the '$' removed; returns the position of the primary suffix
+template <typename string_type, typename output_iterator>
+typename string_type::index_type bwt(
+    const typename string_type::index_type  string_len,
+    string_type                             string,
+    output_iterator                         output,
+    BWTParams*                              params)
+{
+    (void)params;
+    const uint64 n = string_len;
+    sufsort::check_length(n);
+    sufsort::packed_text<string_type> text(n, string);
+    const uint64 tb = nvbio_hip_bwt_temp_bytes(n);
+    sufsort::scratch temp(tb);
+    sufsort::scratch words(4u * ((n + 63u) / 64u) * 4u);
+    uint32 primary = 0;
+    sufsort::check(nvbio_hip_bwt(text.words, 2u, text.big_endian, n, 0u, words.as<uint32>(), &primary, nullptr, nullptr, temp.ptr, tb, nullptr), "nvbio_hip_bwt");
+    const uint32 phase   = sufsort::word_phase<output_iterator>::get(output);
+    const uint64 n_lanes = (n + phase + 15u) / 16u;
+    hipLaunchKernelGGL((sufsort::unpack_kernel<output_iterator>), dim3(uint32((n_lanes + 255u) / 256u)), dim3(256), 0, 0, n, words.as<uint32>(), output, phase, n_lanes);
+    sufsort::check(hipGetLastError(), "unpack_kernel");
+    sufsort::check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    return typename string_type::index_type(primary);
+}
+
+/// return the position of the primary suffix of a string
+template <typename string_type>
+typename string_type::index_type find_primary(
+    const typename string_type::index_type  string_len,
+    const string_type                       string)
+{
+    const uint64 n = string_len;
+    sufsort::check_length(n);
+    sufsort::packed_text<string_type> text(n, string);
+    const uint64 tb = nvbio_hip_bwt_temp_bytes(n);
+    sufsort::scratch temp(tb);
+    sufsort::scratch words(4u * ((n + 63u) / 64u) * 4u);
+    uint32 primary = 0;
+    sufsort::check(nvbio_hip_bwt(text.words, 2u, text.big_endian, n, 0u, words.as<uint32>(), &primary, nullptr, nullptr, temp.ptr, tb, nullptr), "nvbio_hip_bwt");
+    return typename string_type::index_type(primary);
+}
+
+} // namespace cuda
+} // namespace nvbio

@@ -32,6 +32,8 @@ SYMBOLS = [
     "nvbio_hip_fm_extend_host", "nvbio_hip_fm_mem_rank_host", "nvbio_hip_fm_mem_locate_host",
     "nvbio_hip_fm_mem_split_temp_bytes", "nvbio_hip_fm_mem_rank_split", "nvbio_hip_fm_mem_rank_split_host",
     "nvbio_hip_build_bwt_occ_temp_bytes", "nvbio_hip_build_bwt_occ",
+    "nvbio_hip_suffix_sort_temp_bytes", "nvbio_hip_suffix_sort", "nvbio_hip_suffix_sort_last_rounds", "nvbio_hip_bwt_temp_bytes", "nvbio_hip_bwt",
+    "nvbio_hip_suffix_sort_host", "nvbio_hip_bwt_host",
     "nvbio_hip_device_malloc", "nvbio_hip_device_free", "nvbio_hip_device_free_ordered", "nvbio_hip_device_free_after", "nvbio_hip_device_trim", "nvbio_hip_device_mem_info", "nvbio_hip_memcpy", "nvbio_hip_memset",
     "nvbio_hip_stream_synchronize", "nvbio_hip_stream_query", "nvbio_hip_host_malloc", "nvbio_hip_host_free", "nvbio_hip_stream_create", "nvbio_hip_stream_destroy",
     "nvbio_hip_comm_available", "nvbio_hip_device_count", "nvbio_hip_set_device", "nvbio_hip_get_device", "nvbio_hip_comm_unique_id", "nvbio_hip_comm_init_rank",
@@ -227,6 +229,16 @@ def lib():
         L.nvbio_hip_build_bwt_occ_temp_bytes.argtypes = [u32]
         L.nvbio_hip_build_bwt_occ_temp_bytes.restype = u64
         L.nvbio_hip_build_bwt_occ.argtypes = [u32, vp, vp, vp, vp, u64, vp]
+        L.nvbio_hip_suffix_sort_temp_bytes.argtypes = [u64]
+        L.nvbio_hip_suffix_sort_temp_bytes.restype = u64
+        L.nvbio_hip_suffix_sort.argtypes = [vp, u32, u32, u64, vp, vp, u64, vp]
+        L.nvbio_hip_suffix_sort_last_rounds.argtypes = [P(u64), u32]
+        L.nvbio_hip_suffix_sort_last_rounds.restype = u32
+        L.nvbio_hip_bwt_temp_bytes.argtypes = [u64]
+        L.nvbio_hip_bwt_temp_bytes.restype = u64
+        L.nvbio_hip_bwt.argtypes = [vp, u32, u32, u64, u32, vp, P(u32), vp, vp, vp, u64, vp]
+        L.nvbio_hip_suffix_sort_host.argtypes = [vp, u32, u32, u64, vp, i32]
+        L.nvbio_hip_bwt_host.argtypes = [vp, u32, u32, u64, u32, vp, P(u32), vp, vp, i32]
         L.nvbio_hip_comm_unique_id.argtypes = [vp]
         L.nvbio_hip_comm_init_rank.argtypes = [P(vp), C.c_int, C.c_int, vp]
         L.nvbio_hip_comm_init_all.argtypes = [vp, C.c_int, vp]

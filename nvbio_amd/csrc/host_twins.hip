@@ -427,3 +427,94 @@ NVB_API int nvbio_hip_fm_mem_locate_host(const nvbio_hip_fmindex* f_fmi, const u
     }
     return hipSuccess;
 }
+
+// ---- suffix sorting and BWT of one 2-bit text (sufsort.hip): prefix doubling with std::sort, the same convention, the same bytes ----
+namespace {
+
+inline uint32 text_symbol(const uint32* words, const uint32 be, const uint64 i)
+{
+    const uint32 k = uint32(i & 15u);
+    return (words[i >> 4] >> (be ? 30u - 2u * k : 2u * k)) & 3u;
+}
+
+int suffix_sort_host(const uint32* words, const uint32 be, const uint64 n, uint32* sa, const int threads)
+{
+    // rank 0 = past the end, so a suffix that is a prefix of another sorts first; symbols are 1..4 in the first round
+    std::vector<uint32> rank(n), next(n);
+    std::vector<uint64> key(n);
+    uint32* rows = sa + 1;
+    sa[0] = uint32(n);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 i = 0; i < int64(n); ++i) { rows[i] = uint32(i); rank[i] = text_symbol(words, be, uint64(i)) + 1u; }
+    for (uint64 h = 1;; h *= 2u)
+    {
+        #pragma omp parallel for schedule(static) num_threads(threads)
+        for (int64 i = 0; i < int64(n); ++i)
+            key[i] = (uint64(rank[i]) << 32) | (uint64(i) + h < n ? rank[uint64(i) + h] : 0u);
+        std::sort(rows, rows + n, [&](const uint32 a, const uint32 b) { return key[a] < key[b]; });
+        uint32 groups = 0;
+        for (uint64 k = 0; k < n; ++k)
+        {
+            if (k == 0 || key[rows[k]] != key[rows[k - 1u]]) ++groups;
+            next[rows[k]] = groups;
+        }
+        rank.swap(next);
+        if (groups == n) return hipSuccess;
+    }
+}
+
+inline int sufsort_args(const uint32* words, const uint32 bits, const uint64 n)
+{
+    return (!words || bits != 2u || n == 0u || n > 0xFFFFFFFEull) ? int(hipErrorInvalidValue) : int(hipSuccess);
+}
+
+} // anonymous namespace
+
+NVB_API int nvbio_hip_suffix_sort_host(const uint32_t* words, uint32_t bits, uint32_t big_endian, uint64_t n, uint32_t* sa_out, int32_t n_threads)
+{
+    if (int e = sufsort_args(words, bits, n)) return e;
+    if (!sa_out) return hipErrorInvalidValue;
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#else
+    const int threads = 1;
+#endif
+    return suffix_sort_host(words, big_endian ? 1u : 0u, n, sa_out, threads);
+}
+
+NVB_API int nvbio_hip_bwt_host(const uint32_t* words, uint32_t bits, uint32_t big_endian, uint64_t n, uint32_t sa_int, uint32_t* bwt_words_out,
+                               uint32_t* primary_out, uint32_t* ssa_out, uint32_t* sa_out, int32_t n_threads)
+{
+    if (int e = sufsort_args(words, bits, n)) return e;
+    if (!bwt_words_out || !primary_out || (ssa_out && sa_int == 0u)) return hipErrorInvalidValue;
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#else
+    const int threads = 1;
+#endif
+    std::vector<uint32> own;
+    if (!sa_out) { own.resize(n + 1u); sa_out = own.data(); }
+    const uint32 be = big_endian ? 1u : 0u;
+    if (int e = suffix_sort_host(words, be, n, sa_out, threads)) return e;
+    uint64 primary = 0;
+    for (uint64 r = 0; r <= n; ++r) if (sa_out[r] == 0u) { primary = r; break; }
+    *primary_out = uint32(primary);
+    const uint64 n_words = 4u * ((n + 63u) / 64u);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 w = 0; w < int64(n_words); ++w)
+    {
+        uint32 out = 0u;
+        for (uint32 q = 0; q < 16u; ++q)
+        {
+            const uint64 j = uint64(w) * 16u + q;
+            if (j < n) out |= text_symbol(words, be, uint64(sa_out[j + (j >= primary ? 1u : 0u)]) - 1u) << (30u - 2u * q);
+        }
+        bwt_words_out[w] = out;
+    }
+    if (ssa_out)
+    {
+        const uint64 n_ssa = (n + sa_int) / sa_int;
+        for (uint64 k = 0; k < n_ssa; ++k) ssa_out[k] = k ? sa_out[k * sa_int] : 0xFFFFFFFFu;
+    }
+    return hipSuccess;
+}
