@@ -1159,6 +1159,7 @@ const char* nvbio_hip_arch(void);           /* "gfx950" */
 const char* nvbio_hip_last_kernel(void);    /* name of the last kernel variant launched by this thread */
 const char* nvbio_hip_last_kernel_detail(void);  /* "pair" if that launch was the banded 16-bit LOCAL kernel in its two-jobs-per-lane form, else "" */
 const char* nvbio_hip_last_kernel_cell(void);    /* the cell of a "pair" launch: "max3" (three-input maxima) or "u16" (two-input ones), else "" */
+const char* nvbio_hip_last_kernel_frame(void);   /* the frame of a "pair" launch's cell: "column" (no gap subtract on the horizontal step) or "row", else "" */
 const char* nvbio_hip_last_kernel_fetch(void);   /* how a "pair" launch read its strings: "stream" (32-bit cursors, only new words loaded) or "generic", else "" */
 
 #ifdef __cplusplus

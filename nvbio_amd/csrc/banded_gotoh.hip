@@ -52,6 +52,7 @@ thread_local const char* g_last_kernel = "";
 thread_local const char* g_last_pair = nullptr;
 thread_local const char* g_last_pair_cell = "";
 thread_local const char* g_last_pair_fetch = "";
+thread_local const char* g_last_pair_frame = "";
 
 #define NVB_DECL(B) \
     extern template hipError_t launch_band_width<B, NoQual>(const GotohParams&, const NoQual&, int, bool, hipStream_t); \
@@ -69,7 +70,8 @@ NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
 
 #define NVB_DECL(F) \
     extern template hipError_t launch_band_pair<15, P16, (F)>(const GotohParams&, hipStream_t); \
-    extern template hipError_t launch_band_pair<15, PM3, (F)>(const GotohParams&, hipStream_t);
+    extern template hipError_t launch_band_pair<15, PM3, (F)>(const GotohParams&, hipStream_t); \
+    extern template hipError_t launch_band_pair<15, PD3, (F)>(const GotohParams&, hipStream_t);
 NVB_DECL(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_DECL)
 #undef NVB_DECL
 
@@ -141,7 +143,8 @@ static uint32_t max_len_16bit(int32_t match, int32_t best_pair /* max substituti
 // is its limit too.  What it needs besides: fixed-length strings, no row that sees a symbol past the text's end (N >= M + BAND - 1: the
 // compare form is not built), scores that fit the byte table (0 <= mismatch - G_o, max(match, mismatch) - G_o <= 7, so that
 // (s - G_o) * 32 <= 255), and G_o <= G_e <= 0, so that S = h + (G_o - G_e) and E + G_e are subtractions of magnitudes.
-// NVBIO_HIP_BANDED_PAIR: 0 = the pair form where admitted, 1 = never, 2 = the pair form with the u16 cell only.
+// NVBIO_HIP_BANDED_PAIR: 0 = the pair form where admitted, 1 = never, 2 = the pair form with the u16 cell only, 3 = the pair form with
+// the row-frame cells only (max3, then u16).
 static bool pair_admitted(const GotohParams& p, int type, uint32_t band, uint32_t lim16)
 {
     if (test_switch(SW_BANDED_PAIR) == 1 || type != NVBIO_HIP_LOCAL || band != 15u) return false;
@@ -185,6 +188,22 @@ static bool pair_max3_admitted(const GotohParams& p)
     return int64_t(p.pat.fixed_length) * per_row <= PM3_ROW_LIMIT;
 }
 
+// The max3 cell in the column frame (banded_gotoh_pair.h: PD3) is taken where PM3 would be and its own two bounds hold.
+//   * The table's byte.  A diagonal step crosses 2 G of the column frame where it crosses G of the row frame, so the substitution byte is
+//     32 (s - G_o) + G = 32 (s - G_o + |G_e|), which fits 255 while max(match, mismatch) - G_o + |G_e| <= 7 (PD3_BYTE_LIMIT).
+//   * The top of the f16 range.  The frame's zero is Z(i,j) = 0x0400 + D + G + G (2 i + j + 2), at most 0x0400 + D + G + G (2 M + 14) in
+//     the last row's last column, and H <= M S+ with S+ = max(match, mismatch, 0); so the largest h' is Z(M-1,14) + 32 M S+.  The operands
+//     above an h' are its key, h' + K_j = 32 H + Z(i,14) + j <= that + 14, and a diagonal, S' + byte = (h' - D) + byte of the row before,
+//     which the largest h' plus a whole byte covers: pd3_top() = 0x0400 + D + G + G (2 M + 14) + 32 M S+ + 255 must not pass 0x7BFF
+//     (PD3_TOP).  (2,-1,-2,-1) is admitted up to M = 234, where the bound is met exactly; longer jobs keep PM3 (to 312) and P16 (to 340).
+static bool pair_column_admitted(const GotohParams& p)
+{
+    if (test_switch(SW_BANDED_PAIR) == 3 || !pair_max3_admitted(p)) return false;
+    const int64_t s_max = std::max(p.match, p.mismatch), G = -int64_t(p.gap_ext) * 32, D = (int64_t(p.gap_ext) - p.gap_open) * 32;
+    if (s_max - p.gap_open - p.gap_ext > PD3_BYTE_LIMIT) return false;
+    return pd3_top(D, G, p.pat.fixed_length, std::max<int64_t>(s_max, 0)) <= PD3_TOP;
+}
+
 } // namespace nvb
 
 template <typename QA>
@@ -196,6 +215,7 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
     g_last_pair = nullptr;
     g_last_pair_cell = "";
     g_last_pair_fetch = "";
+    g_last_pair_frame = "";
     // NVBIO_HIP_FORCE_32BIT=1 disables the 16-bit kernels (used by the tests to cover both widths)
     // the row-frame kernels' limit (the plain launch); the limit of the recurrence as written (asymmetric costs, the bounded form -- and LOCAL jobs
     // between the two limits, which the plain launch hands to the A16P instance)
@@ -236,8 +256,10 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
     if (plain_entry && pair_admitted(p, type, band_len, lim16)) {
         g_last_kernel = g_last_pair = tag16;
         const bool max3 = pair_max3_admitted(p);
+        const bool column = max3 && pair_column_admitted(p);
         g_last_pair_cell = max3 ? "max3" : "u16";
-        return max3 ? launch_pair<PM3>(p, s) : launch_pair<P16>(p, s);
+        g_last_pair_frame = column ? "column" : "row";
+        return column ? launch_pair<PD3>(p, s) : max3 ? launch_pair<PM3>(p, s) : launch_pair<P16>(p, s);
     }
     if (lim16 > 0 && (!fixed || patterns->fixed_length <= lim16)) {
         p.len_lo = 0; p.len_hi = lim16;
@@ -722,4 +744,5 @@ NVB_API const char* nvbio_hip_arch(void)        { return "gfx950"; }
 NVB_API const char* nvbio_hip_last_kernel(void) { return nvb::g_last_kernel; }
 NVB_API const char* nvbio_hip_last_kernel_detail(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? "pair" : ""; }
 NVB_API const char* nvbio_hip_last_kernel_fetch(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_fetch : ""; }
+NVB_API const char* nvbio_hip_last_kernel_frame(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_frame : ""; }
 NVB_API const char* nvbio_hip_last_kernel_cell(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_cell : ""; }

@@ -44,6 +44,35 @@
 //   * E = max(E, S) stays a two-input maximum.
 // An interior cell is then 8.5 vector instructions, 3.5 of them maxima, where P16 has 11 and 6.
 //
+// The column frame.  PD3 is PM3 in a frame that also rises along the row: phi(i,j) = BIAS' + G (2 (i + 1) + j), so the zero of row i,
+// column j is Z(i,j) = BIAS' + G (2 i + j + 2) and h' = 32 H + Z(i,j), S' = h' - D as before.  The three steps of the recurrence:
+//   * horizontal, (i,j) -> (i,j+1): phi rises by G, the cost of the step, so E'(i,j+1) = max(E'(i,j), S'(i,j)) with no subtract; column 0
+//     has no E and hands its S' to column 1 as E'(i,1);
+//   * vertical, (i-1,j+1) -> (i,j): phi rises by 2 G - G = G, free as in the row frame: F'(i,j) = max3(F'(i-1,j+1), S'(i-1,j+1), Z(i,j));
+//   * diagonal, (i-1,j) -> (i,j): phi rises by 2 G, one G more than in the row frame, which the substitution byte carries:
+//     32 (s - G_o) + G.  It fits while max(match, mismatch) - G_o + |G_e| <= 7 (PD3_BYTE_LIMIT).
+//   * F' = max(F, Z) carries over: the zero along the F path does not fall, Z(i-1,j+1) = Z(i,j) - G <= Z(i,j), so with
+//     F'(-1,.) = 0x0400 <= Z(0,.) the induction of PM3 reads the same with Z(i,j) for Z_i:
+//       F'(i,j) = max(max(F(i-1,j+1), Z(i-1,j+1)), S'(i-1,j+1), Z(i,j)) = max(F(i,j), Z(i,j)).
+//     The infimum argument is unchanged (every S' is a real value at or above Z - D >= 0x0400).
+//   * the row key must compare columns in one frame: key_j = h'(i,j) + K_j with K_j = j + (14 - j) G is 32 H + Z(i,14) + j, column 14's
+//     frame -- the add the tag j costs anyway, with another constant (and one more add, for column 0, whose K_0 = 14 G is not zero).  The
+//     sink takes Z(i,14) off the row key and folds p = score * 32 + j as before.
+//   * Z(i,j) depends on 2 i + j alone and is wave-uniform: a ring of 16 scalar registers at index (2 i + j) & 15.  Row i holds
+//     2 i ... 2 i + 14; its prologue adds 16 G to the two slots no row reads any more (2 i - 3 and 2 i - 2 become 2 i + 13 and 2 i + 14),
+//     two scalar adds where the row frame has one vector add.  The rows are unrolled 16 to a block and 2 * 16 = 0 (mod 16), so every
+//     index is static.  K_j and D are scalars too: every instruction of the cell takes at most one of them.
+//   * start: S'(-1,j) = Z(-1,j) - D = BIAS' + G j - D (H = 0 in row -1), F' = 0x0400, Z(0,j) = BIAS' + G (2 + j).
+//   * no carry, no borrow: the only subtracts left are S' = h' - D with h' >= Z(i,j) >= BIAS' > D, and the sink's, Z(i,14) from a row
+//     key >= key_0 = h'(i,0) + 14 G >= Z(i,0) + 14 G = Z(i,14).  The smallest value is F'(-1,.) = 0x0400; every S', E' >= Z - D >= 0x0400 + G.
+//   * the top: h' <= Z(M-1,14) + 32 M S+ = BIAS' + G (2 M + 14) + 32 M S+; a key adds at most 14 to an h' (K_j <= 14 G moves column j's
+//     value into column 14's frame, it does not pass that frame's top) and a diagonal adds a byte to an S' = h' - D of the row before, so
+//     pd3_top() = 0x0400 + D + G + G (2 M + 14) + 32 M S+ + 255 <= 0x7BFF keeps every operand in range; the scalar adds stay below it too
+//     (Z <= h', K_j <= 14 G <= Z(0,14)).  The frame costs range -- G (2 M + 14) where the row frame spends G M -- so the host admits it for
+//     shorter jobs than PM3 (banded_gotoh.hip: pair_column_admitted; M <= 234 under (2,-1,-2,-1)) and PM3 takes the rest.
+// A row loses 14 of its 30 subtracts (12 interior cells, the cell next to the edge and column 0) and the vector add of its zero, and
+// gains column 0's key add: 128 vector instructions where PM3 has 142, and the chain E -> h -> S -> E is three instructions long, not four.
+//
 // The sink.  Un-framed (its row's zero taken off), a job's row key is p = score * 32 + j: the row's best score and the largest column
 // that holds it, 16 bits.  The fold's rule is "replace when (p | 31) >= best": the higher score wins, and on an equal score the later
 // row.  The library folds it with a compare and two selects per job (PF_SINK_VCC), the key in one register and its row in another.
@@ -84,6 +113,7 @@ enum PairForm : int {
 
 // what both cells share: the replicated constants, the substitution lookup and the sink
 struct PairOps {
+    static constexpr bool COLUMN = false;                                           // the row frame (PD3 alone holds the column frame)
     static __device__ __forceinline__ uint32_t rep(int32_t c)               { return (uint32_t(c) & 0xFFFFu) * 0x10001u; }
     static __device__ __forceinline__ uint32_t mx(uint32_t a, uint32_t b)   { uint32_t r; asm("v_pk_max_u16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
     // both jobs' text symbols of one band column as one byte selector: {g_A, zero, 4 + g_B, zero} picks entry g_A of tlo and g_B of thi
@@ -93,9 +123,11 @@ struct PairOps {
     // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here.  The fold, the probe's key form of it
     // (the header comment, "The sink") and the probe's knock-out, which keeps the row key live through one packed maximum
     template <int FORM, int BAND>
-    static __device__ __forceinline__ void sink(PairState<BAND>& st, uint32_t rowkey, const uint32_t i)
+    static __device__ __forceinline__ void sink(PairState<BAND>& st, uint32_t rowkey, const uint32_t i) { fold<FORM>(st, rowkey - st.z, i); }
+    // rowkey: un-framed
+    template <int FORM, int BAND>
+    static __device__ __forceinline__ void fold(PairState<BAND>& st, const uint32_t rowkey, const uint32_t i)
     {
-        rowkey -= st.z;
         if (FORM & PF_KO_SINK) { st.best[0] = mx(st.best[0], rowkey); return; }
         if (FORM & PF_SINK_KEY)
         {
@@ -296,29 +328,171 @@ struct PM3 : PairOps {
     }
 };
 
+// ---- the max3 cell in the column frame: E pays no gap subtract, the row's zeros and the cell's constants are scalars (the header
+// comment, "The column frame")
+// the largest operand of a PD3 maximum (a diagonal of the last row's last column), which must not pass PD3_TOP; D, G times 32 as in the kernel
+constexpr int32_t PD3_TOP = 0x7BFF, PD3_BYTE_LIMIT = 7;                            // 7 >= max(match, mismatch) - G_o + |G_e|: the table's byte
+constexpr int64_t pd3_top(int64_t D, int64_t G, int64_t M, int64_t s_plus, int64_t band = 15)
+{
+    return 0x0400 + D + G + G * (2 * M + band - 1) + 32 * M * s_plus + 255;
+}
+// what a wave shares, all of it in scalar registers: the ring of the row's zeros, Z(i,j) at index (2 i + j) & 15; the keys' constants
+// K_j = j + (BAND - 1 - j) G; D; the ring's step 16 G
+template <int BAND>
+struct ColumnFrame {
+    uint32_t z[16];
+    uint32_t k[BAND];
+    uint32_t D, step;
+};
+struct PD3 : PairOps {
+    static constexpr bool COLUMN = true;
+    static constexpr int32_t FLOOR = 0x0400;
+
+    // column 0 (no E): F' = max3(F'(i-1,1), S'(i-1,1), Z(i,0)), h = max(F', diagonal); its key seeds the row key, its S' is column 1's E'
+    static __device__ __forceinline__ void col0(uint32_t& F0, const uint32_t F1, uint32_t& S0, const uint32_t S1, uint32_t& rowkey,
+                                                const uint32_t g0, const uint32_t D, const uint32_t tlo, const uint32_t thi, const uint32_t Z0, const uint32_t K0)
+    {
+        uint32_t d, h;
+        asm("v_perm_b32 %[d], %[thi], %[tlo], %[g0]\n\t"
+            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t"
+            "v_add_u32 %[d], %[s0], %[d]\n\t"
+            "v_pk_max_u16 %[h], %[f0], %[d]\n\t"
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
+            "v_add_u32 %[rk], %[k0], %[h]"
+            : [f0] "=&v"(F0), [d] "=&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
+            : [g0] "v"(g0), [tlo] "v"(tlo), [thi] "v"(thi), [f1] "v"(F1), [s1] "v"(S1), [dd] "s"(D), [z0] "s"(Z0), [k0] "s"(K0));
+    }
+
+    // PM3::cell2 without E's subtracts: E'(J+1) = max(E'(J), S'(J)).  Ein: E'(i,J), read only (column 1's is S'(i,0), which stays live as
+    // the next row's diagonal); E: E'(i,J+2).  Z0, Z1: Z(i,J), Z(i,J+1); K0, K1: K_J, K_(J+1); they and D are scalars, one to an instruction
+    static __device__ __forceinline__ void cell2(uint32_t& F0, uint32_t& F1, const uint32_t F2, uint32_t& S0, uint32_t& S1, const uint32_t S2, const uint32_t Ein, uint32_t& E,
+                                                 uint32_t& rowkey, const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
+                                                 const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
+    {
+        uint32_t d0, d1, h;
+        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
+            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t"
+            "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z1]\n\t"
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
+            "v_add_u32 %[d0], %[k0], %[h]\n\t"
+            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f1], %[d1], %[e]\n\t"
+            "v_subrev_u32 %[s1], %[dd], %[h]\n\t"
+            "v_add_u32 %[d1], %[k1], %[h]\n\t"
+            "v_pk_max_u16 %[e], %[e], %[s1]\n\t"
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+            : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
+            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein),
+              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+    }
+
+    // PM3::tail2 in the column frame: the cell J next to the band's edge (F' = max(S'(i-1,J+1), Z(i,J))) and the last column J + 1
+    // (h = max3(E', diagonal, Z(i,J+1)))
+    static __device__ __forceinline__ void tail2(uint32_t& F0, uint32_t& S0, uint32_t& S1, const uint32_t Ein, uint32_t& rowkey,
+                                                 const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
+                                                 const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
+    {
+        uint32_t d0, d1, h, e;
+        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
+            "v_pk_max_u16 %[f0], %[s1], %[z0]\n\t"
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
+            "v_add_u32 %[d0], %[k0], %[h]\n\t"
+            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
+            "v_pk_maximum3_f16 %[h], %[e], %[d1], %[z1]\n\t"
+            "v_subrev_u32 %[s1], %[dd], %[h]\n\t"
+            "v_add_u32 %[d1], %[k1], %[h]\n\t"
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+            : [f0] "=&v"(F0), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
+            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [ei] "v"(Ein),
+              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+    }
+
+    template <int BAND, int R, int J, int END>
+    struct Cells {
+        static __device__ __forceinline__ void run(PairState<BAND>& st, const ColumnFrame<BAND>& fr, const uint32_t Ein, uint32_t& E, uint32_t& rowkey, const uint32_t tlo, const uint32_t thi)
+        {
+            uint32_t En;
+            cell2(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
+                  fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
+            Cells<BAND, R, J + 2, END>::run(st, fr, En, E, rowkey, tlo, thi);
+        }
+    };
+    template <int BAND, int R, int END>
+    struct Cells<BAND, R, END, END> {
+        static __device__ __forceinline__ void run(PairState<BAND>&, const ColumnFrame<BAND>&, const uint32_t Ein, uint32_t& E, uint32_t&, uint32_t, uint32_t) { E = Ein; }
+    };
+
+    // the wave's frame before row 0: slot s of the ring holds Z(0, s) = BIAS' + G (2 + s) for the columns row 0's prologue leaves alone and
+    // 16 G less for the two it advances (and for slot 15, which row 1 advances before its first use)
+    template <int BAND>
+    static __device__ __forceinline__ void open(ColumnFrame<BAND>& fr, const int32_t d32, const int32_t g32)
+    {
+        #pragma unroll
+        for (int s = 0; s < 16; ++s) fr.z[s] = rep(d32 + g32 + FLOOR + g32 * (2 + (s <= BAND - 3 ? s : s - 16)));
+        #pragma unroll
+        for (int j = 0; j < BAND; ++j) fr.k[j] = rep(j + (BAND - 1 - j) * g32);
+        fr.D = rep(d32);
+        fr.step = rep(16 * g32);
+    }
+
+    template <int BAND, int R, int FORM>
+    static __device__ __forceinline__ void row(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
+    {
+        static_assert(BAND == 15, "a row's zeros, 2 i ... 2 i + BAND - 1, and the two the next row adds fill the ring of 16; columns go two at a time");
+        // this row's zeros: Z(i, BAND-2) and Z(i, BAND-1) take the slots of Z(i-1, 0) - G and Z(i-1, 0); scalar adds
+        fr.z[(2 * R + BAND - 2) & 15] += fr.step;
+        fr.z[(2 * R + BAND - 1) & 15] += fr.step;
+        uint32_t rowkey, E;
+        col0(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, st.tc[R & 15], fr.D, tlo, thi, fr.z[(2 * R) & 15], fr.k[0]);
+        // 1 <= j <= BAND-3, then BAND-2 and BAND-1
+        Cells<BAND, R, 1, BAND - 2>::run(st, fr, st.S[0], E, rowkey, tlo, thi);
+        st.tc[(R + BAND - 1) & 15] = g_new;
+        tail2(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
+              fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        fold<FORM>(st, rowkey - fr.z[(2 * R + BAND - 1) & 15], i);                    // the row key stands in the last column's frame
+    }
+};
+
 template <typename CELL, int BAND, int FORM, int R, int END>
 struct PairRows {
     // XT[0] / XT[1]: the block's entering text symbols 0-7 / 8-15, job A's in the low half and job B's in the high half
     // (KT: the resident table of the probe's PF_KO_TABLE, otherwise unused)
-    static __device__ __forceinline__ void run(PairState<BAND>& st, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
+    // fr: the column frame's scalars (CELL::COLUMN; the row-frame cells take D and G instead)
+    static __device__ __forceinline__ void run(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
                                                const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab, const uint32_t (&KT)[2])
     {
         if ((FORM & PF_KO_BOUND) || i0 + R < M)
         {
             const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
-            if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, KT[0], KT[1]);
-            else                    CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
+            if constexpr (CELL::COLUMN)
+            {
+                if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, KT[0], KT[1]);
+                else                    CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
+            }
+            else
+            {
+                if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, KT[0], KT[1]);
+                else                    CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
+            }
         }
-        PairRows<CELL, BAND, FORM, R + 1, END>::run(st, i0, M, D, G, PA, PB, XT, tab, KT);
+        PairRows<CELL, BAND, FORM, R + 1, END>::run(st, fr, i0, M, D, G, PA, PB, XT, tab, KT);
     }
 };
 template <typename CELL, int BAND, int FORM, int END> struct PairRows<CELL, BAND, FORM, END, END> {
-    static __device__ __forceinline__ void run(PairState<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2]) {}
+    static __device__ __forceinline__ void run(PairState<BAND>&, ColumnFrame<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2]) {}
 };
 
 // Lane k of the launch takes jobs 2k and 2k + 1 (with an odd n the last lane computes its one job in both halves).  The host has
 // checked (banded_gotoh.hip: pair_admitted) that every job has M >= 1 rows, that no row sees a symbol past the text's end and that the
-// scheme's scores fit the byte table, and for CELL = PM3 that M (S+ + |G_e|) <= PM3_ROW_LIMIT.  The strings are read from HBM per 16-row block: staging them in LDS as banded_gotoh_score_kernel
+// scheme's scores fit the byte table, for CELL = PM3 and PD3 that M (S+ + |G_e|) <= PM3_ROW_LIMIT, and for PD3 its byte and its top (pair_column_admitted).  The strings are read from HBM per 16-row block: staging them in LDS as banded_gotoh_score_kernel
 // does (two slots per lane) measured no faster with 256 lanes and slower with 128 (profiles/banded_pair/README.md), so there is none.
 // FORM & PF_STREAM: the host has also checked that both word arrays are short enough for GroupStream's 32-bit byte offsets and has
 // picked the instance of the pattern's width and the two byte orders (PF_PAT2, PF_PBE, PF_TBE), so the loop tests none of them; it
@@ -334,7 +508,9 @@ banded_gotoh_pair_kernel(const GotohParams p)
     __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
     if (threadIdx.x < 16u)
     {
-        const uint32_t sm = uint32_t((p.match - p.gap_open) * 32), sx = uint32_t((p.mismatch - p.gap_open) * 32);
+        // (the column frame's diagonal step rises by 2 G where the row frame's rises by G: the table carries the other G)
+        const uint32_t tg = CELL::COLUMN ? uint32_t(-p.gap_ext * 32) : 0u;
+        const uint32_t sm = uint32_t((p.match - p.gap_open) * 32) + tg, sx = uint32_t((p.mismatch - p.gap_open) * 32) + tg;
         uint32_t t = sx * 0x01010101u;
         if (threadIdx.x < 4u) t = (t & ~(0xFFu << (8u * threadIdx.x))) | (sm << (8u * threadIdx.x));
         s_tab[threadIdx.x] = t;
@@ -349,16 +525,18 @@ banded_gotoh_pair_kernel(const GotohParams p)
 
     const int32_t d32 = (p.gap_ext - p.gap_open) * 32, g32 = -p.gap_ext * 32;
     uint32_t D = CELL::rep(d32), G = CELL::rep(g32);
-    asm("" : "+v"(D)); asm("" : "+v"(G));                                         // resident, like A16::pin
+    if (!CELL::COLUMN) { asm("" : "+v"(D)); asm("" : "+v"(G)); }                  // resident, like A16::pin (the column frame keeps its constants in scalars)
     uint32_t KT[2] = { 0u, 0u };
     if (FORM & PF_KO_TABLE) { KT[0] = s_tab[threadIdx.x & 3u]; KT[1] = s_tab[(threadIdx.x >> 2) & 3u]; asm("" : "+v"(KT[0])); asm("" : "+v"(KT[1])); }
 
     PairState<BAND> st;
     #pragma unroll
-    for (int j = 0; j < BAND; ++j) st.S[j] = CELL::rep(g32 + CELL::FLOOR);          // H = 0 in row -1: BIAS - D
+    for (int j = 0; j < BAND; ++j) st.S[j] = CELL::rep(g32 + CELL::FLOOR + (CELL::COLUMN ? g32 * j : 0));   // H = 0 in row -1: BIAS - D (+ G j in the column frame)
     #pragma unroll
     for (int j = 0; j < BAND - 1; ++j) st.F[j] = CELL::rep(CELL::FLOOR);
     st.z = CELL::rep(d32 + g32 + CELL::FLOOR);                                     // BIAS
+    ColumnFrame<BAND> fr;
+    if constexpr (CELL::COLUMN) CELL::open(fr, d32, g32);                          // (st.z is not used then)
     st.best[0] = st.best[1] = 0u; st.besti[0] = st.besti[1] = 0u;
     {
         const uint32_t TA = fetch16_2bit(ts[0], tb[0]), TB = fetch16_2bit(ts[1], tb[1]);
@@ -404,7 +582,7 @@ banded_gotoh_pair_kernel(const GotohParams p)
             TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1); TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
         }
         const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
-        PairRows<CELL, BAND, FORM, 0, 16>::run(st, i0, M, D, G, PA, PB, XT, s_tab, KT);
+        PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, PA, PB, XT, s_tab, KT);
         if (FORM & PF_KO_FETCH)
         {
             PA = (PA << 4) | (PA >> 60); PB = (PB << 8) | (PB >> 56);

@@ -16,6 +16,8 @@ extern thread_local const char* g_last_pair;
 extern thread_local const char* g_last_pair_cell;
 // how its block loop read the strings, "stream" or "generic": nvbio_hip_last_kernel_fetch
 extern thread_local const char* g_last_pair_fetch;
+// the frame its cell holds, "column" (PD3) or "row" (PM3, P16): nvbio_hip_last_kernel_frame
+extern thread_local const char* g_last_pair_frame;
 
 // Test switches (include/nvbio_hip.h, "Test switches"): alternative executions of the same results.  Each is an atomic int, seeded ONCE
 // from the environment variable of the same name (std::call_once) and changed afterwards only through nvbio_hip_set_test_switch --

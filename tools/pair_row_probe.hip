@@ -1,4 +1,5 @@
-// pair_row_probe.hip -- where a row of banded_gotoh_pair_kernel<15, PM3> spends its cycles outside its cells.
+// pair_row_probe.hip -- where a row of banded_gotoh_pair_kernel<15, PM3> spends its cycles outside its cells, and what the same row costs
+// with the column frame's cell (PD3).
 //
 // Launches the real kernel template (nvbio_amd/csrc/banded_gotoh_pair.h) in its forms and in knock-out variants of them on strings
 // generated on the device in the headline's layout: 100-symbol reads, 4 bits big-endian, back to back; 150-symbol windows, 2 bits
@@ -24,6 +25,7 @@ thread_local const char* g_last_kernel = nullptr;
 thread_local const char* g_last_pair = nullptr;
 thread_local const char* g_last_pair_cell = "";
 thread_local const char* g_last_pair_fetch = "";
+thread_local const char* g_last_pair_frame = "";
 int test_switch(TestSwitch) { return 0; }
 }
 using namespace nvb;
@@ -75,6 +77,7 @@ __global__ void make_begins(uint64_t* pb, uint64_t* tb, uint32_t n)
 struct Variant { const char* name; const char* what; hipError_t (*launch)(const GotohParams&, hipStream_t); uint32_t rows; bool results; };
 
 #define FORM(f) launch_band_pair<15, PM3, (f)>
+#define COLF(f) launch_band_pair<15, PD3, (f)>
 constexpr int STREAMED = PF_STREAM | PF_PBE;               // the streamed form of these strings: 4-bit big-endian reads, little-endian windows
 static const Variant VARIANTS[] = {
     { "K0",        "nothing: generic fetches (the form before the streamed one)",      FORM(PF_SINK_VCC), READ, true },
@@ -90,6 +93,12 @@ static const Variant VARIANTS[] = {
     { "stream-K2", "streamed words without the LDS table reads",                       FORM(STREAMED | PF_KO_TABLE), READ, false },
     { "stream/96", "streamed words, 96 rows (stream-K4's yardstick)",                  FORM(STREAMED), 96, true },
     { "stream-K4", "streamed words without the per-row bound test, 96 rows",           FORM(STREAMED | PF_KO_BOUND), 96, false },
+    // the column frame's cell in the same forms: the whole kernel beside K0 and stream, the cells alone beside K5
+    { "col-K0",    "column frame, nothing: generic fetches",                           COLF(PF_SINK_VCC), READ, true },
+    { "col-K0/96", "column frame, nothing, 96 rows (col-K5's yardstick)",              COLF(PF_SINK_VCC), 96, true },
+    { "col-K5",    "column frame, K1 to K4 together, 96 rows: cells only",             COLF(PF_KO_SINK | PF_KO_TABLE | PF_KO_FETCH | PF_KO_BOUND), 96, false },
+    { "col-stream","column frame, streamed words (what the library launches)",         COLF(STREAMED), READ, true },
+    { "col-stream/96", "column frame, streamed words, 96 rows",                        COLF(STREAMED), 96, true },
 };
 
 int main(int argc, char** argv)
