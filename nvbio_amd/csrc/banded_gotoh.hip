@@ -53,6 +53,7 @@ thread_local const char* g_last_pair = nullptr;
 thread_local const char* g_last_pair_cell = "";
 thread_local const char* g_last_pair_fetch = "";
 thread_local const char* g_last_pair_frame = "";
+thread_local const char* g_last_pair_row = "";
 
 #define NVB_DECL(B) \
     extern template hipError_t launch_band_width<B, NoQual>(const GotohParams&, const NoQual&, int, bool, hipStream_t); \
@@ -71,7 +72,8 @@ NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
 #define NVB_DECL(F) \
     extern template hipError_t launch_band_pair<15, P16, (F)>(const GotohParams&, hipStream_t); \
     extern template hipError_t launch_band_pair<15, PM3, (F)>(const GotohParams&, hipStream_t); \
-    extern template hipError_t launch_band_pair<15, PD3, (F)>(const GotohParams&, hipStream_t);
+    extern template hipError_t launch_band_pair<15, PD3, (F)>(const GotohParams&, hipStream_t); \
+    extern template hipError_t launch_band_pair<15, PD3, (F) | PF_ROW2>(const GotohParams&, hipStream_t);
 NVB_DECL(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_DECL)
 #undef NVB_DECL
 
@@ -162,18 +164,27 @@ static bool pair_stream_admitted(const GotohParams& p)
 {
     return p.pat.s.bits != 8u && p.pat.s.n_words <= (1ull << 29) && p.txt.s.n_words <= (1ull << 29);
 }
-template <typename CELL>
-static hipError_t launch_pair(const GotohParams& p, hipStream_t s)
+// ROW: PF_ROW2 for the column frame's cell (its sink folded once per two rows), 0 for the row as it was, which the row-frame cells
+// keep and NVBIO_HIP_PAIR_ROW = 1 asks for.  nvbio_hip_last_kernel_row() says which one ran.
+template <typename CELL, int ROW>
+static hipError_t launch_pair_row(const GotohParams& p, hipStream_t s)
 {
+    g_last_pair_row = ROW ? "fold2" : "plain";
     g_last_pair_fetch = "generic";
-    if (!pair_stream_admitted(p)) return launch_band_pair<15, CELL, PF_SINK_VCC>(p, s);
+    if (!pair_stream_admitted(p)) return launch_band_pair<15, CELL, PF_SINK_VCC | ROW>(p, s);
     g_last_pair_fetch = "stream";
     switch (PF_STREAM | (p.pat.s.bits == 2u ? PF_PAT2 : 0) | (p.pat.s.big_endian ? PF_PBE : 0) | (p.txt.s.big_endian ? PF_TBE : 0)) {
-#define NVB_CASE(F) case (F): return launch_band_pair<15, CELL, (F)>(p, s);
+#define NVB_CASE(F) case (F): return launch_band_pair<15, CELL, (F) | ROW>(p, s);
     NVB_PAIR_STREAM_FORMS(NVB_CASE)
 #undef NVB_CASE
     }
     return hipErrorNotSupported;
+}
+template <typename CELL>
+static hipError_t launch_pair(const GotohParams& p, hipStream_t s)
+{
+    if constexpr (CELL::COLUMN) { if (test_switch(SW_PAIR_ROW) != 1) return launch_pair_row<CELL, PF_ROW2>(p, s); }
+    return launch_pair_row<CELL, 0>(p, s);
 }
 
 // The max3 cell of the pair form (banded_gotoh_pair.h: PM3) takes its maxima with v_pk_maximum3_f16, which is an exact unsigned maximum
@@ -216,6 +227,7 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
     g_last_pair_cell = "";
     g_last_pair_fetch = "";
     g_last_pair_frame = "";
+    g_last_pair_row = "";
     // NVBIO_HIP_FORCE_32BIT=1 disables the 16-bit kernels (used by the tests to cover both widths)
     // the row-frame kernels' limit (the plain launch); the limit of the recurrence as written (asymmetric costs, the bounded form -- and LOCAL jobs
     // between the two limits, which the plain launch hands to the A16P instance)
@@ -691,7 +703,7 @@ namespace nvb {
 static std::atomic<int> g_switch[SW_COUNT];
 static const char* const g_switch_name[SW_COUNT] = { "NVBIO_HIP_FORCE_32BIT", "NVBIO_HIP_NO_STAGING", "NVBIO_HIP_FULL_GENERIC", "NVBIO_HIP_ED_SWEEP",
                                                      "NVBIO_HIP_FULL_SINGLE_JOB", "NVBIO_HIP_FULL_ROWS", "NVBIO_HIP_TRACEBACK_LANES", "NVBIO_HIP_SELECT_LANES",
-                                                     "NVBIO_HIP_BANDED_PAIR" };
+                                                     "NVBIO_HIP_BANDED_PAIR", "NVBIO_HIP_PAIR_ROW" };
 static void seed_switches()
 {
     static std::once_flag once;
@@ -745,4 +757,5 @@ NVB_API const char* nvbio_hip_last_kernel(void) { return nvb::g_last_kernel; }
 NVB_API const char* nvbio_hip_last_kernel_detail(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? "pair" : ""; }
 NVB_API const char* nvbio_hip_last_kernel_fetch(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_fetch : ""; }
 NVB_API const char* nvbio_hip_last_kernel_frame(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_frame : ""; }
+NVB_API const char* nvbio_hip_last_kernel_row(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_row : ""; }
 NVB_API const char* nvbio_hip_last_kernel_cell(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_cell : ""; }

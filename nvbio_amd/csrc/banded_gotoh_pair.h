@@ -82,6 +82,28 @@
 // 0-4.  Unsigned order on W is the order of (score, row, column), and every row folds a different i, so the maximum over the rows is
 // the fold's result; the epilogue decodes score = W >> 20, i = (W >> 5) & 1023, j = W & 31.  It needs score <= 1023 and i <= 1023,
 // three instructions fewer per row, and measured no faster (profiles/banded_pair/README.md), so the library does not take it.
+//
+// The pair fold.  PF_FOLD2, which the library takes for PD3, folds once per two rows.  A column is at most 14, so bit 4 of the key is
+// free: rows i (even) and i + 1 share the key q = score * 32 + 16 r + j, r the row's parity, and besti holds the even row.  A plain
+// maximum over q is the fold's order inside a pair -- the higher score, on equal scores row i + 1 whatever the columns, inside a row
+// the larger column -- and "(q | 31) >= best" keeps "the later row wins" across pairs.  The epilogue decodes j = best & 15,
+// row = besti + ((best >> 4) & 1), score = best >> 5.
+//   * frames: a row key stands in its row's last-column frame and Z(i+1,14) = Z(i,14) + 2 G, so the even row's key stays live across
+//     the row boundary (one VGPR) and the odd row takes  q = max(rk(i) + 2 G, rk(i+1) + 16) - Z(i+1,14):  two adds and a packed
+//     maximum per pair in place of one whole fold (the subtract is the fold's own).
+//   * range: both operands of that maximum are row keys in the odd row's frame.  rk(i) + 2 G = 32 H + Z(i+1,14) + j is what row i + 1
+//     would hold for the same H, and rk(i+1) + 16 adds the pair's bit to a key: at most 14 + 16 = 30 above an h' of row i + 1, where
+//     "the top" leaves 255 above the largest h'; and both are at least Z(i+1,14) >= 0x0400 -- no key is lowered below its zero (in
+//     the all-zero scheme Z is 0x0400 itself).  No add carries (the sums stay below 0x7BFF) and the subtract does not borrow (both
+//     operands are >= Z(i+1,14)).  pair_column_admitted is unchanged.
+//   * an odd number of rows: the last row has no partner.  Its key is still live behind the block loop and is folded there alone, as
+//     its pair's even row (q = rk(M-1) - Z(M-1,14), bit 4 clear), with Z(M-1,14) = BIAS' + G (2 M + 14) worked out once per job.
+//   tests/test_pair_fold2.py holds the arithmetic in numpy.
+//
+// Two forms that did not pay, kept for tools/pair_row_probe.hip alone (profiles/banded_pair/README.md has the figures).  PF_AHEAD
+// issues row R + 1's two table reads at the head of row R, hidden from the compiler in asm (it sinks a load it sees to its use), and
+// waits for them at the head of row R + 1: the same instructions, no exposed LDS round trip -- and no faster, the other four waves
+// of the SIMD were covering it.  PF_ORDER is cell2 / tail2 with the chain links E' -> h -> S' apart from each other: no faster either.
 #pragma once
 #include "banded_gotoh_impl.h"
 
@@ -104,8 +126,14 @@ enum PairForm : int {
     PF_STREAM   = 4,                                                                // the block loop streams its words (GroupStream, common.h), and then:
     PF_PAT2     = 2,                                                                //   the pattern has 2 bits (else 4)
     PF_PBE      = 8, PF_TBE = 256,                                                  //   the pattern's / the text's words are big-endian
-    PF_KO_SINK  = 16, PF_KO_TABLE = 32, PF_KO_FETCH = 64, PF_KO_BOUND = 128         // probe only
+    PF_KO_SINK  = 16, PF_KO_TABLE = 32, PF_KO_FETCH = 64, PF_KO_BOUND = 128,        // probe only
+    // the column frame's row (the header comment, "The pair fold" and "Two forms that did not pay"):
+    PF_FOLD2    = 1024,                                                             //   the sink folds a pair of rows at a time
+    PF_AHEAD    = 512,                                                              //   a row's table words are read while the row before runs (probe only)
+    PF_ORDER    = 2048                                                              //   the cells' chain links interleaved with their independent work (probe only)
 };
+// the row the library launches for PD3 (banded_gotoh.hip: launch_pair; NVBIO_HIP_PAIR_ROW = 1 keeps the row without it)
+constexpr int PF_ROW2 = PF_FOLD2;
 // the streamed forms the library holds: every pattern width and byte order it streams
 #define NVB_PAIR_STREAM_FORMS(X) \
     X(PF_STREAM) X(PF_STREAM | PF_PBE) X(PF_STREAM | PF_TBE) X(PF_STREAM | PF_PBE | PF_TBE) \
@@ -119,6 +147,25 @@ struct PairOps {
     // both jobs' text symbols of one band column as one byte selector: {g_A, zero, 4 + g_B, zero} picks entry g_A of tlo and g_B of thi
     static constexpr uint32_t SEL_BASE = 0x0C040C00u;
     static __device__ __forceinline__ uint32_t subst(uint32_t tlo, uint32_t thi, uint32_t sel) { return __builtin_amdgcn_perm(thi, tlo, sel); }
+
+    // PF_AHEAD (probe only): a table word read that the compiler does not see, so that it cannot sink it to its use: issued a row ahead, waited for
+    // by table_wait before the first cell reads it.  Every table_ahead is followed on every path by a table_wait naming its destination
+    // (PairRows::run, and the block loop's wait behind the rows).  addr: the LDS byte address.  before: a register the row's first cell
+    // reads, passed through untouched -- the cells' asm blocks are not volatile, and without it the compiler puts them ahead of the read
+    // and issues it a few instructions before the next row's wait
+    static __device__ __forceinline__ void table_ahead(uint32_t& t, const uint32_t addr, uint32_t& before)
+    {
+        asm volatile("ds_read_b32 %0, %2" : "=v"(t), "+v"(before) : "v"(addr));
+    }
+    static __device__ __forceinline__ void table_wait(uint32_t& tlo, uint32_t& thi)      { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tlo), "+v"(thi)); }
+    static __device__ __forceinline__ void table_wait(uint32_t (&t)[4])
+    {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
+    }
+    static __device__ __forceinline__ uint32_t lds_address(const uint32_t* shared)
+    {
+        return uint32_t(uintptr_t((const __attribute__((address_space(3))) uint32_t*)shared));
+    }
 
     // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here.  The fold, the probe's key form of it
     // (the header comment, "The sink") and the probe's knock-out, which keeps the row key live through one packed maximum
@@ -343,6 +390,7 @@ struct ColumnFrame {
     uint32_t z[16];
     uint32_t k[BAND];
     uint32_t D, step;
+    uint32_t pair;           // 2 G, what a row key gains on its way into the next row's frame (PF_FOLD2)
 };
 struct PD3 : PairOps {
     static constexpr bool COLUMN = true;
@@ -390,6 +438,34 @@ struct PD3 : PairOps {
               [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
     }
 
+    // PF_ORDER (probe only): cell2's fifteen instructions in another order, one more temporary.  No instruction reads the result of the
+    // one before it where independent work is left to put between them: the second v_perm, the second F', cell J + 1's diagonal add and
+    // cell J's key add stand between the links of E' -> h -> S'
+    static __device__ __forceinline__ void cell2_ordered(uint32_t& F0, uint32_t& F1, const uint32_t F2, uint32_t& S0, uint32_t& S1, const uint32_t S2, const uint32_t Ein, uint32_t& E,
+                                                         uint32_t& rowkey, const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
+                                                         const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
+    {
+        uint32_t d0, d1, h, h1;
+        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
+            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t"
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
+            "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z1]\n\t"
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
+            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
+            "v_add_u32 %[d0], %[k0], %[h]\n\t"
+            "v_pk_maximum3_f16 %[h1], %[f1], %[d1], %[e]\n\t"
+            "v_subrev_u32 %[s1], %[dd], %[h1]\n\t"
+            "v_add_u32 %[d1], %[k1], %[h1]\n\t"
+            "v_pk_max_u16 %[e], %[e], %[s1]\n\t"
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+            : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [h1] "=&v"(h1), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
+            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein),
+              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+    }
+
     // PM3::tail2 in the column frame: the cell J next to the band's edge (F' = max(S'(i-1,J+1), Z(i,J))) and the last column J + 1
     // (h = max3(E', diagonal, Z(i,J+1)))
     static __device__ __forceinline__ void tail2(uint32_t& F0, uint32_t& S0, uint32_t& S1, const uint32_t Ein, uint32_t& rowkey,
@@ -415,18 +491,46 @@ struct PD3 : PairOps {
               [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
     }
 
-    template <int BAND, int R, int J, int END>
+    // PF_ORDER (probe only): tail2's thirteen instructions in the order of cell2_ordered
+    static __device__ __forceinline__ void tail2_ordered(uint32_t& F0, uint32_t& S0, uint32_t& S1, const uint32_t Ein, uint32_t& rowkey,
+                                                         const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
+                                                         const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
+    {
+        uint32_t d0, d1, h, h1, e;
+        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
+            "v_pk_max_u16 %[f0], %[s1], %[z0]\n\t"
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
+            "v_add_u32 %[d0], %[k0], %[h]\n\t"
+            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
+            "v_pk_maximum3_f16 %[h1], %[e], %[d1], %[z1]\n\t"
+            "v_subrev_u32 %[s1], %[dd], %[h1]\n\t"
+            "v_add_u32 %[d1], %[k1], %[h1]\n\t"
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+            : [f0] "=&v"(F0), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [h1] "=&v"(h1), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
+            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [ei] "v"(Ein),
+              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+    }
+
+    template <int BAND, int R, int FORM, int J, int END>
     struct Cells {
         static __device__ __forceinline__ void run(PairState<BAND>& st, const ColumnFrame<BAND>& fr, const uint32_t Ein, uint32_t& E, uint32_t& rowkey, const uint32_t tlo, const uint32_t thi)
         {
             uint32_t En;
-            cell2(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
-                  fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
-            Cells<BAND, R, J + 2, END>::run(st, fr, En, E, rowkey, tlo, thi);
+            if constexpr ((FORM & PF_ORDER) != 0)
+                cell2_ordered(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
+                              fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
+            else
+                cell2(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
+                      fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
+            Cells<BAND, R, FORM, J + 2, END>::run(st, fr, En, E, rowkey, tlo, thi);
         }
     };
-    template <int BAND, int R, int END>
-    struct Cells<BAND, R, END, END> {
+    template <int BAND, int R, int FORM, int END>
+    struct Cells<BAND, R, FORM, END, END> {
         static __device__ __forceinline__ void run(PairState<BAND>&, const ColumnFrame<BAND>&, const uint32_t Ein, uint32_t& E, uint32_t&, uint32_t, uint32_t) { E = Ein; }
     };
 
@@ -441,10 +545,12 @@ struct PD3 : PairOps {
         for (int j = 0; j < BAND; ++j) fr.k[j] = rep(j + (BAND - 1 - j) * g32);
         fr.D = rep(d32);
         fr.step = rep(16 * g32);
+        fr.pair = rep(2 * g32);
     }
 
+    // rk2 (PF_FOLD2): the even row's row key, which waits for the odd row's
     template <int BAND, int R, int FORM>
-    static __device__ __forceinline__ void row(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i, const uint32_t g_new, const uint32_t tlo, const uint32_t thi)
+    static __device__ __forceinline__ void row(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i, const uint32_t g_new, const uint32_t tlo, const uint32_t thi, uint32_t& rk2)
     {
         static_assert(BAND == 15, "a row's zeros, 2 i ... 2 i + BAND - 1, and the two the next row adds fill the ring of 16; columns go two at a time");
         // this row's zeros: Z(i, BAND-2) and Z(i, BAND-1) take the slots of Z(i-1, 0) - G and Z(i-1, 0); scalar adds
@@ -453,12 +559,37 @@ struct PD3 : PairOps {
         uint32_t rowkey, E;
         col0(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, st.tc[R & 15], fr.D, tlo, thi, fr.z[(2 * R) & 15], fr.k[0]);
         // 1 <= j <= BAND-3, then BAND-2 and BAND-1
-        Cells<BAND, R, 1, BAND - 2>::run(st, fr, st.S[0], E, rowkey, tlo, thi);
+        Cells<BAND, R, FORM, 1, BAND - 2>::run(st, fr, st.S[0], E, rowkey, tlo, thi);
         st.tc[(R + BAND - 1) & 15] = g_new;
-        tail2(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
-              fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
-        fold<FORM>(st, rowkey - fr.z[(2 * R + BAND - 1) & 15], i);                    // the row key stands in the last column's frame
+        if constexpr ((FORM & PF_ORDER) != 0)
+            tail2_ordered(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
+                          fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        else
+            tail2(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
+                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        if constexpr ((FORM & PF_FOLD2) != 0)
+        {
+            // the header comment, "The pair fold": the even row's key moves into the odd row's frame (2 G up), the odd row's takes the
+            // pair's bit, and one fold serves both under the even row's number
+            if constexpr ((R & 1) == 0) rk2 = rowkey;
+            else fold<FORM>(st, mx(rk2 + fr.pair, rowkey + rep(16)) - fr.z[(2 * R + BAND - 1) & 15], i - 1u);
+        }
+        else fold<FORM>(st, rowkey - fr.z[(2 * R + BAND - 1) & 15], i);               // the row key stands in the last column's frame
     }
+
+    // PF_FOLD2, an odd number of rows: the last row has no partner and is folded alone as its pair's even row.  Its zero Z(M-1, BAND-1)
+    // is worked out here, once per job
+    template <int BAND, int FORM>
+    static __device__ __forceinline__ void fold_last(PairState<BAND>& st, const uint32_t rk2, const uint32_t M, const int32_t d32, const int32_t g32)
+    {
+        fold<FORM>(st, rk2 - rep(d32 + g32 + FLOOR + g32 * int32_t(2u * M + BAND - 1)), M - 1u);
+    }
+};
+
+// what the column frame's row carries from one row to the next (PF_AHEAD, PF_FOLD2; unused otherwise)
+struct RowCarry {
+    uint32_t t[4];           // the table words of the even rows, {t[0], t[1]}, and of the odd rows, {t[2], t[3]}: one pair in use, one on its way
+    uint32_t rk2;            // the even row's row key
 };
 
 template <typename CELL, int BAND, int FORM, int R, int END>
@@ -466,16 +597,40 @@ struct PairRows {
     // XT[0] / XT[1]: the block's entering text symbols 0-7 / 8-15, job A's in the low half and job B's in the high half
     // (KT: the resident table of the probe's PF_KO_TABLE, otherwise unused)
     // fr: the column frame's scalars (CELL::COLUMN; the row-frame cells take D and G instead)
+    // PF_AHEAD (probe only): row R waits for its own two table words, issues row R + 1's (rows 1 ... 15; the pattern's nibbles of all sixteen rows are
+    // in PA / PB, and a nibble past the pattern's end still indexes the table's sixteen entries) and then runs its cells.  Row 0 issues
+    // its own first: one exposed wait per block.  The read-ahead does not ask whether row R + 1 will run; the kernel waits once more
+    // behind the block's rows, so that no read is in flight when its register changes hands.
     static __device__ __forceinline__ void run(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
-                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab, const uint32_t (&KT)[2])
+                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab, const uint32_t (&KT)[2], RowCarry& c)
     {
         if ((FORM & PF_KO_BOUND) || i0 + R < M)
         {
             const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
             if constexpr (CELL::COLUMN)
             {
-                if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, KT[0], KT[1]);
-                else                    CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
+                if constexpr ((FORM & PF_AHEAD) != 0)
+                {
+                    constexpr int C = 2 * (R & 1), N = 2 - C;                      // this row's pair of c.t and the next row's
+                    const uint32_t base = CELL::lds_address(tab);
+                    if (R == 0)
+                    {
+                        CELL::table_ahead(c.t[0], base + 4u * (uint32_t(PA) & 15u), st.S[0]);
+                        CELL::table_ahead(c.t[1], base + 4u * (uint32_t(PB) & 15u), st.S[0]);
+                    }
+                    CELL::table_wait(c.t[C], c.t[C + 1]);
+                    if (R + 1 < 16)
+                    {
+                        CELL::table_ahead(c.t[N], base + 4u * (uint32_t(PA >> (4 * ((R + 1) & 15))) & 15u), st.S[0]);
+                        CELL::table_ahead(c.t[N + 1], base + 4u * (uint32_t(PB >> (4 * ((R + 1) & 15))) & 15u), st.S[0]);
+                    }
+                    CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, c.t[C], c.t[C + 1], c.rk2);
+                    // the rows behind one that does not run do not run either: they are asked from inside this one, so that no path
+                    // leads from a read-ahead into a later row past the wait of the row between them
+                    PairRows<CELL, BAND, FORM, R + 1, END>::run(st, fr, i0, M, D, G, PA, PB, XT, tab, KT, c);
+                }
+                else if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, KT[0], KT[1], c.rk2);
+                else                         CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u], c.rk2);
             }
             else
             {
@@ -483,11 +638,11 @@ struct PairRows {
                 else                    CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
             }
         }
-        PairRows<CELL, BAND, FORM, R + 1, END>::run(st, fr, i0, M, D, G, PA, PB, XT, tab, KT);
+        if constexpr (!(FORM & PF_AHEAD)) PairRows<CELL, BAND, FORM, R + 1, END>::run(st, fr, i0, M, D, G, PA, PB, XT, tab, KT, c);
     }
 };
 template <typename CELL, int BAND, int FORM, int END> struct PairRows<CELL, BAND, FORM, END, END> {
-    static __device__ __forceinline__ void run(PairState<BAND>&, ColumnFrame<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2]) {}
+    static __device__ __forceinline__ void run(PairState<BAND>&, ColumnFrame<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2], RowCarry&) {}
 };
 
 // Lane k of the launch takes jobs 2k and 2k + 1 (with an odd n the last lane computes its one job in both halves).  The host has
@@ -503,7 +658,10 @@ __global__ void __launch_bounds__(PAIR_LANES)
 banded_gotoh_pair_kernel(const GotohParams p)
 {
     static_assert(BAND >= 3 && BAND <= 16, "the ring of 16");
-    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0;
+    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0, AHEAD = (FORM & PF_AHEAD) != 0, FOLD2 = (FORM & PF_FOLD2) != 0;
+    static_assert(!(FORM & (PF_AHEAD | PF_FOLD2 | PF_ORDER)) || CELL::COLUMN, "the new row is the column frame's");
+    static_assert(!AHEAD || !(FORM & PF_KO_TABLE), "no table reads, none ahead");
+    static_assert(!FOLD2 || !(FORM & (PF_SINK_KEY | PF_KO_SINK | PF_KO_BOUND)), "the pair fold is the compare-and-select fold's, over the job's own rows");
     constexpr bool P4 = !(FORM & PF_PAT2), PBE = (FORM & PF_PBE) != 0, TBE = (FORM & PF_TBE) != 0;     // STREAM only: the host has matched them to the strings
     __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
     if (threadIdx.x < 16u)
@@ -538,6 +696,7 @@ banded_gotoh_pair_kernel(const GotohParams p)
     ColumnFrame<BAND> fr;
     if constexpr (CELL::COLUMN) CELL::open(fr, d32, g32);                          // (st.z is not used then)
     st.best[0] = st.best[1] = 0u; st.besti[0] = st.besti[1] = 0u;
+    RowCarry carry = { { 0u, 0u, 0u, 0u }, 0u };
     {
         const uint32_t TA = fetch16_2bit(ts[0], tb[0]), TB = fetch16_2bit(ts[1], tb[1]);
         #pragma unroll
@@ -582,7 +741,8 @@ banded_gotoh_pair_kernel(const GotohParams p)
             TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1); TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
         }
         const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
-        PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, PA, PB, XT, s_tab, KT);
+        PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, PA, PB, XT, s_tab, KT, carry);
+        if constexpr (AHEAD) CELL::table_wait(carry.t);                            // the read-ahead of a row that did not run
         if (FORM & PF_KO_FETCH)
         {
             PA = (PA << 4) | (PA >> 60); PB = (PB << 8) | (PB >> 56);
@@ -597,12 +757,14 @@ banded_gotoh_pair_kernel(const GotohParams p)
         else { PA = PAn; PB = PBn; TA = TAn; TB = TBn; }
     }
 
+    if constexpr (FOLD2) { if (M & 1u) CELL::template fold_last<BAND, FORM>(st, carry.rk2, M, d32, g32); }
     #pragma unroll
     for (int h = 0; h < 2; ++h)
     {
         if (h == 1 && id[1] == id[0]) break;
-        // the key sink's best is score << 20 | 31 << 15 | row << 5 | column
-        const uint32_t j = st.best[h] & 31u, i = KEY ? (st.best[h] >> 5) & 1023u : st.besti[h];
+        // the key sink's best is score << 20 | 31 << 15 | row << 5 | column; the pair fold's is score << 5 | odd row << 4 | column beside
+        // the pair's even row
+        const uint32_t j = st.best[h] & (FOLD2 ? 15u : 31u), i = KEY ? (st.best[h] >> 5) & 1023u : st.besti[h] + (FOLD2 ? (st.best[h] >> 4) & 1u : 0u);
         p.out_score[id[h]] = int32_t(st.best[h] >> (KEY ? 20 : 5));
         reinterpret_cast<uint2*>(p.out_sink)[id[h]] = make_uint2(i + j + 1u, i + 1u);
     }

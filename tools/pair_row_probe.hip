@@ -6,15 +6,18 @@
 // little-endian, back to back; scheme (2,-1,-2,-1).  Two warm-up launches, then ten timed ones with HIP events around each.
 // A knock-out takes one part of the row away and keeps its inputs live (PairForm, PF_KO_*); what it prints is a time, never a result.
 // The forms that do compute results print a checksum of scores and sinks, which must be the same for all of them.
+// The last rows are the column frame's row with its table words read a row ahead (PF_AHEAD), its sink folded once per two rows (PF_FOLD2),
+// both, and the cells' instructions in another order (PF_ORDER).
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/pair_row_probe.hip -o tools/pair_row_probe
-//   tools/pair_row_probe [jobs = 10000000] [timed launches = 10]
+//   tools/pair_row_probe [jobs = 10000000] [timed launches = 10] [only the variants whose names begin with this]
 // (fewer than about 10 M jobs are too few rounds of waves per SIMD for the cycles per row to mean much)
 //
 // Counters: run it under the profiler with one counter group and `10000000 1`; every variant is a kernel of its own name.
 #include "../nvbio_amd/csrc/banded_gotoh_pair.h"
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 #include <algorithm>
 #include <vector>
 #define CHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e_)); exit(1); } } while (0)
@@ -26,6 +29,7 @@ thread_local const char* g_last_pair = nullptr;
 thread_local const char* g_last_pair_cell = "";
 thread_local const char* g_last_pair_fetch = "";
 thread_local const char* g_last_pair_frame = "";
+thread_local const char* g_last_pair_row = "";
 int test_switch(TestSwitch) { return 0; }
 }
 using namespace nvb;
@@ -99,13 +103,22 @@ static const Variant VARIANTS[] = {
     { "col-K5",    "column frame, K1 to K4 together, 96 rows: cells only",             COLF(PF_KO_SINK | PF_KO_TABLE | PF_KO_FETCH | PF_KO_BOUND), 96, false },
     { "col-stream","column frame, streamed words (what the library launches)",         COLF(STREAMED), READ, true },
     { "col-stream/96", "column frame, streamed words, 96 rows",                        COLF(STREAMED), 96, true },
+    // the row around the column frame's cells: the pair fold, which the library takes, and the two forms that did not pay; their
+    // checksums must be col-stream's
+    { "col-ahead",  "col-stream, table words read a row ahead",                        COLF(STREAMED | PF_AHEAD), READ, true },
+    { "col-fold2",  "col-stream, the sink folded once per two rows (the library's launch)", COLF(STREAMED | PF_FOLD2), READ, true },
+    { "col-ahead-fold2", "col-stream, both",                                           COLF(STREAMED | PF_AHEAD | PF_FOLD2), READ, true },
+    { "col-order",  "col-stream, the cells' chain links interleaved",                  COLF(STREAMED | PF_ORDER), READ, true },
+    { "col-fold2-order", "col-fold2, the cells' chain links interleaved",              COLF(STREAMED | PF_FOLD2 | PF_ORDER), READ, true },
+    { "col-stream'", "col-stream once more (the run's drift)",                         COLF(STREAMED), READ, true },
 };
 
 int main(int argc, char** argv)
 {
     const uint32_t n = argc > 1 ? uint32_t(strtoul(argv[1], nullptr, 10)) : 10000000u;
     const int timed = argc > 2 ? atoi(argv[2]) : 10;
-    if (n == 0 || n > 20000000u || timed < 1 || timed > 100) { printf("usage: pair_row_probe [jobs <= 20000000] [timed launches <= 100]\n"); return 2; }
+    const char* only = argc > 3 ? argv[3] : "";
+    if (n == 0 || n > 20000000u || timed < 1 || timed > 100) { printf("usage: pair_row_probe [jobs <= 20000000] [timed launches <= 100] [name prefix]\n"); return 2; }
     const uint64_t psym = uint64_t(n) * READ, tsym = uint64_t(n) * WINDOW, pw = (psym + 7u) / 8u + 4u, tw = (tsym + 15u) / 16u + 4u;
     uint32_t *pwords, *twords, *sink; int32_t* score; uint64_t *pbegin, *tbegin;
     CHECK(hipMalloc(&pwords, pw * 4u)); CHECK(hipMalloc(&twords, tw * 4u));
@@ -129,6 +142,7 @@ int main(int argc, char** argv)
     printf("%-14s %-68s %4s  %-26s %12s %12s  %s\n", "variant", "what is removed / which form", "rows", "ms min / median / max", "cyc/row(min)", "cyc/row(med)", "checksum");
     for (const Variant& v : VARIANTS)
     {
+        if (strncmp(v.name, only, strlen(only)) != 0) continue;
         p.pat.fixed_length = v.rows;
         std::vector<float> ms;
         for (int it = 0; it < 2 + timed; ++it)
