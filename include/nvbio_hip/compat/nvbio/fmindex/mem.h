@@ -15,9 +15,13 @@
 // holds occ <= split_width rows is kept, and the (occ + 1)-SMEMs covering its midpoint that pass min_span and max_intv are added, every
 // span once, ordered by begin, then end (the reference replaces the MEM and takes the begins at another threshold than the ends, mem_inl.h:1364-1424).
 // find_threshold_kmems is not provided.
+// Every execution -- the host filter, the lanes of the generic device filter, the C-ABI's `_host` twins -- walks a string with
+// fmindex::walk_kmems and reports through mem_reseed_handler (plain) or mem_split_handler (re-seeding) into a sink; the host ones
+// build their rank table with fmindex::flatten_mems.
 #pragma once
 #include "bidir.h"
 #include "filter.h"
+#include "../basic/algorithms.h"
 #include <algorithm>
 #include <vector>
 
@@ -144,27 +148,12 @@ uint32 find_kmems(const uint32 pattern_len, const pattern_type pattern, const ui
 
 namespace fmindex {
 
-/// collects the MEMs of one string as rank records, applying max_intv
-template <typename coord_type>
-struct mem_collector
+/// the walk over one string, on the host and in a lane: find_kmems from symbol 0, each group starting where the last one's matches end
+template <typename pattern_type, typename fm_index_type, typename delegate_type, typename store_type>
+NVBIO_FORCEINLINE NVBIO_HOST_DEVICE
+void walk_kmems(const uint32 len, const pattern_type& s, const fm_index_type& f_index, const fm_index_type& r_index,
+                delegate_type& handler, const uint32 min_intv, const uint32 min_span, store_type& store, uint64* n_records = NULL)
 {
-    typedef typename vector_type<coord_type, 2u>::type range_type;
-    mem_collector(std::vector< MEMRange<coord_type> >& out, const uint32 id, const uint32 max_intv_) : ranges(out), string_id(id), max_intv(max_intv_) {}
-    void output(const range_type range, const uint2 span)
-    {
-        if (coord_type(coord_type(1u) + range.y - range.x) <= max_intv) ranges.push_back(MEMRange<coord_type>(range, string_id, span));
-    }
-    std::vector< MEMRange<coord_type> >& ranges; uint32 string_id; uint32 max_intv;
-};
-
-/// every reported MEM of a string, begin ascending
-template <typename string_type, typename fm_index_type>
-void string_mems(const string_type& s, const uint32 len, const uint32 string_id, const fm_index_type& f_index, const fm_index_type& r_index,
-                 const uint32 min_intv, const uint32 max_intv, const uint32 min_span,
-                 std::vector< MEMRange<typename fm_index_type::index_type> >& out, std::vector<uint4>& store, uint64* n_records = NULL)
-{
-    mem_collector<typename fm_index_type::index_type> handler(out, string_id, max_intv);
-    if (store.size() < size_t(len) + 1u) store.resize(size_t(len) + 1u);
     for (uint32 x = 0; x < len;)
     {
         const uint32 e = find_kmems(len, s, x, f_index, r_index, handler, min_intv, min_span, store, n_records);
@@ -176,7 +165,7 @@ void string_mems(const string_type& s, const uint32 len, const uint32 string_id,
 // candidate; its re-seeds are the (occ + 1)-SMEMs covering (b + e) >> 1 -- one find_kmems at that symbol and threshold -- kept iff
 // they pass min_span and max_intv.  The spans go to a `sink` (output(range, span)) that makes the union.
 
-/// the delegate of a re-seed: applies max_intv and hands the span to the sink
+/// the delegate of a walk that does not re-seed, and of a re-seed: applies max_intv and hands the span to the sink
 template <typename coord_type, typename sink_type>
 struct mem_reseed_handler
 {
@@ -234,6 +223,20 @@ struct mem_span_less
     bool operator() (const MEMRange<coord_type>& a, const MEMRange<coord_type>& b) const { return span_key(uint32(a.coords.w)) < span_key(uint32(b.coords.w)); }
 };
 
+/// every reported MEM of a string appended to `out`, begin ascending
+template <typename string_type, typename fm_index_type>
+void string_mems(const string_type& s, const uint32 len, const uint32 string_id, const fm_index_type& f_index, const fm_index_type& r_index,
+                 const uint32 min_intv, const uint32 max_intv, const uint32 min_span,
+                 std::vector< MEMRange<typename fm_index_type::index_type> >& out, std::vector<uint4>& store, uint64* n_records = NULL)
+{
+    typedef typename fm_index_type::index_type coord_type;
+    typedef mem_vector_sink<coord_type>        sink_type;
+    sink_type sink(out, string_id);
+    mem_reseed_handler<coord_type, sink_type> handler(sink, max_intv);
+    if (store.size() < size_t(len) + 1u) store.resize(size_t(len) + 1u);
+    walk_kmems(len, s, f_index, r_index, handler, min_intv, min_span, store, n_records);
+}
+
 /// every reported MEM of a string and the re-seeds of its candidates appended to `out`, each span once, ordered by begin, then
 /// end; returns the number of spans found before the duplicates were removed
 template <typename string_type, typename fm_index_type>
@@ -248,11 +251,7 @@ uint64 string_mems_split(const string_type& s, const uint32 len, const uint32 st
     if (store.size()  < size_t(len) + 1u) store.resize(size_t(len) + 1u);
     if (store2.size() < size_t(len) + 1u) store2.resize(size_t(len) + 1u);
     mem_split_handler<string_type, fm_index_type, sink_type, std::vector<uint4> > handler(len, s, f_index, r_index, sink, store2, max_intv, min_span, split_len, split_width, n_records);
-    for (uint32 x = 0; x < len;)
-    {
-        const uint32 e = find_kmems(len, s, x, f_index, r_index, handler, min_intv, min_span, store, n_records);
-        x = e > x + 1u ? e : x + 1u;
-    }
+    walk_kmems(len, s, f_index, r_index, handler, min_intv, min_span, store, n_records);
     const uint64 found = out.size() - first;
     std::sort(out.begin() + first, out.end(), mem_span_less<coord_type>());
     size_t kept = first;
@@ -260,6 +259,26 @@ uint64 string_mems_split(const string_type& s, const uint32 len, const uint32 st
         if (k == first || out[k].coords.w != out[k - 1u].coords.w) out[kept++] = out[k];
     out.resize(kept);
     return found;
+}
+
+/// the rank table of a batch from the MEMs of each string: index[q] = the first record of string q (n + 1 entries), then record
+/// `at` goes to put(at, record) and slots[at] = the rows of the records up to it, for the first `capacity` records; returns the rows
+/// of the records stored
+template <typename coord_type, typename put_type>
+uint64 flatten_mems(const std::vector< std::vector< MEMRange<coord_type> > >& per_string, const uint64 capacity, uint64* index, put_type put, uint64* slots)
+{
+    index[0] = 0;
+    for (size_t q = 0; q < per_string.size(); ++q) index[q + 1u] = index[q] + per_string[q].size();
+    uint64 sum = 0;
+    for (size_t q = 0; q < per_string.size(); ++q)
+        for (size_t k = 0; k < per_string[q].size(); ++k)
+        {
+            const uint64 at = index[q] + k;
+            if (at >= capacity) return sum;
+            put(at, per_string[q][k]);
+            sum += uint64(per_string[q][k].range_size()); slots[at] = sum;
+        }
+    return sum;
 }
 
 } // namespace fmindex
@@ -305,23 +324,16 @@ struct MEMFilter<host_tag, fm_index_type>
                                                per_string[q], store, store2);
             }
         }
-        m_index.assign(m_n_queries + 1u, 0u);
+        uint64 total = 0;
         for (int64 q = 0; q < n; ++q)
         {
             if (length(string_set[uint32(q)]) > 65535u) throw std::runtime_error("MEMFilter::rank: a pattern is longer than 65 535 symbols");
-            m_index[q + 1] = m_index[q] + per_string[q].size();
+            total += per_string[q].size();
         }
-        m_mem_ranges.resize(m_index[m_n_queries]);
-        m_slots.resize(m_index[m_n_queries]);
-        uint64 sum = 0;
-        for (int64 q = 0; q < n; ++q)
-            for (size_t k = 0; k < per_string[q].size(); ++k)
-            {
-                const uint64 at = m_index[q] + k;
-                m_mem_ranges[at] = per_string[q][k];
-                sum += uint64(per_string[q][k].range_size()); m_slots[at] = sum;
-            }
-        m_n_occurrences = sum;
+        m_index.resize(m_n_queries + 1u);
+        m_mem_ranges.resize(total);
+        m_slots.resize(total);
+        m_n_occurrences = fmindex::flatten_mems(per_string, total, m_index.data(), [this](const uint64 at, const rank_type& r) { m_mem_ranges[at] = r; }, m_slots.data());
         return m_n_occurrences;
     }
 
@@ -338,8 +350,7 @@ struct MEMFilter<host_tag, fm_index_type>
         for (int64 h = 0; h < n; ++h)
         {
             const uint64 g = begin + uint64(h);
-            uint64 lo = 0, hi = n_ranges;
-            while (lo < hi) { const uint64 mid = lo + (hi - lo) / 2u; if (m_slots[mid] <= g) lo = mid + 1u; else hi = mid; }
+            const uint64 lo = nvbio::upper_bound_index(g, m_slots.data(), n_ranges);
             const rank_type& r = m_mem_ranges[lo];
             const coord_type row = coord_type(r.coords.x + coord_type(g - (lo ? m_slots[lo - 1u] : 0u)));
             mems[h] = mem_type(nvbio::locate(m_f_index, row), r.string_id(), r.span());
@@ -398,11 +409,7 @@ __global__ void __launch_bounds__(128) mem_rank_kernel(const uint32 n, const ind
     const uint32 len = uint32(length(s)) < max_len ? uint32(length(s)) : max_len;
     uint4* my_store = store + size_t(q) * max_len;
     mem_lane_handler<typename index_type::index_type> handler = { index ? out : NULL, sizes, index ? index[q] : 0u, 0u, q, max_intv };
-    for (uint32 x = 0; x < len;)
-    {
-        const uint32 e = find_kmems(len, s, x, f_index, r_index, handler, min_intv, min_span, my_store);
-        x = e > x + 1u ? e : x + 1u;
-    }
+    walk_kmems(len, s, f_index, r_index, handler, min_intv, min_span, my_store);
     if (!index) counts[q] = handler.n;
 }
 /// the sink of a re-seeding lane: counts every span and, given the string's segment of the staging table, puts it at its place
@@ -449,11 +456,7 @@ __global__ void __launch_bounds__(128) mem_rank_split_kernel(const uint32 n, con
     uint4* my_store2 = my_store + max_len;
     sink_type sink = { raw_index ? staging + raw_index[q] : NULL, 0u, 0u, q };
     mem_split_handler<string_type, index_type, sink_type, uint4*> handler(len, s, f_index, r_index, sink, my_store2, max_intv, min_span, split_len, split_width, NULL);
-    for (uint32 x = 0; x < len;)
-    {
-        const uint32 e = find_kmems(len, s, x, f_index, r_index, handler, min_intv, min_span, my_store);
-        x = e > x + 1u ? e : x + 1u;
-    }
+    walk_kmems(len, s, f_index, r_index, handler, min_intv, min_span, my_store);
     if (raw_index)
         for (uint32 k = sink.kept; k < sink.raw; ++k) sink.seg[k] = MEMRange<coord_type>(make_vector(coord_type(0u), coord_type(0u)), q, make_uint2(0u, 0u));
     counts[q] = raw_index ? sink.kept : sink.raw;
@@ -479,8 +482,7 @@ __global__ void __launch_bounds__(128) mem_locate_kernel(const uint64 begin, con
     const uint32 h = blockIdx.x * 128u + threadIdx.x;
     if (h >= n_hits) return;
     const uint64 g = begin + h;
-    uint64 lo = 0, hi = n_ranges;
-    while (lo < hi) { const uint64 mid = lo + (hi - lo) / 2u; if (slots[mid] <= g) lo = mid + 1u; else hi = mid; }
+    const uint64 lo = nvbio::upper_bound_index(g, slots, n_ranges);
     if (lo >= n_ranges) return;
     const MEMRange<coord_type> r = ranges[lo];
     const coord_type row = coord_type(r.coords.x + coord_type(g - (lo ? slots[lo - 1u] : 0u)));
@@ -545,23 +547,16 @@ struct MEMFilter<device_tag, fm_index_type>
             uint4*  store     = reinterpret_cast<uint4*>(m_store.reserve(uint64(n) * 2u * max_len * sizeof(uint4)));
             uint64* raw_index = m_raw_index.reserve(uint64(n) + 1u);
             fmindex::check(hipMemsetAsync(raw_index, 0, sizeof(uint64), m_stream), "hipMemsetAsync");
-            hipLaunchKernelGGL((fmindex::mem_rank_split_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
-                               string_set, k, max_intv, min_span, split_len, split_width, store, max_len, raw_index + 1, (const uint64*)NULL, (rank_type*)NULL);
-            fmindex::check(hipGetLastError(), "mem_rank_split_kernel");
-            scan(raw_index + 1, n);
-            uint64 raw = 0, total = 0;
-            fmindex::check(hipMemcpyAsync(&raw, raw_index + n, sizeof(uint64), hipMemcpyDeviceToHost, m_stream), "hipMemcpyAsync");
-            fmindex::check(hipStreamSynchronize(m_stream), "hipStreamSynchronize");
-            if (raw > 0x7FFFFFFFull) throw std::runtime_error("MEMFilter::rank: more than 2^31 - 1 MEMs in one call");
+            const uint64 raw = count_pass(raw_index + 1, n, "mem_rank_split_kernel", [&]() {
+                hipLaunchKernelGGL((fmindex::mem_rank_split_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
+                                   string_set, k, max_intv, min_span, split_len, split_width, store, max_len, raw_index + 1, (const uint64*)NULL, (rank_type*)NULL); });
+            uint64 total = 0;
             if (raw)
             {
                 rank_type* staging = m_staging.reserve(raw);
-                hipLaunchKernelGGL((fmindex::mem_rank_split_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
-                                   string_set, k, max_intv, min_span, split_len, split_width, store, max_len, index + 1, (const uint64*)raw_index, staging);
-                fmindex::check(hipGetLastError(), "mem_rank_split_kernel");
-                scan(index + 1, n);
-                fmindex::check(hipMemcpyAsync(&total, index + n, sizeof(uint64), hipMemcpyDeviceToHost, m_stream), "hipMemcpyAsync");
-                fmindex::check(hipStreamSynchronize(m_stream), "hipStreamSynchronize");
+                total = count_pass(index + 1, n, "mem_rank_split_kernel", [&]() {
+                    hipLaunchKernelGGL((fmindex::mem_rank_split_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
+                                       string_set, k, max_intv, min_span, split_len, split_width, store, max_len, index + 1, (const uint64*)raw_index, staging); });
                 rank_type* ranges = m_mem_ranges.reserve(total);
                 uint64*    slots  = m_slots.reserve(total);
                 hipLaunchKernelGGL((fmindex::mem_compact_kernel<coord_type>), dim3((uint32(raw) + 127u) / 128u), dim3(128), 0, m_stream, uint32(raw),
@@ -575,14 +570,9 @@ struct MEMFilter<device_tag, fm_index_type>
         else if (!tuned)
         {
             uint4* store = reinterpret_cast<uint4*>(m_store.reserve(uint64(n) * max_len * sizeof(uint4)));
-            hipLaunchKernelGGL((fmindex::mem_rank_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
-                               string_set, k, max_intv, min_span, store, max_len, index + 1, (const uint64*)NULL, (rank_type*)NULL, (uint64*)NULL);
-            fmindex::check(hipGetLastError(), "mem_rank_kernel");
-            scan(index + 1, n);
-            uint64 total = 0;
-            fmindex::check(hipMemcpyAsync(&total, index + n, sizeof(uint64), hipMemcpyDeviceToHost, m_stream), "hipMemcpyAsync");
-            fmindex::check(hipStreamSynchronize(m_stream), "hipStreamSynchronize");
-            if (total > 0x7FFFFFFFull) throw std::runtime_error("MEMFilter::rank: more than 2^31 - 1 MEMs in one call");
+            const uint64 total = count_pass(index + 1, n, "mem_rank_kernel", [&]() {
+                hipLaunchKernelGGL((fmindex::mem_rank_kernel<fm_index_type, string_set_type>), dim3((n + 127u) / 128u), dim3(128), 0, m_stream, n, m_f_index, m_r_index,
+                                   string_set, k, max_intv, min_span, store, max_len, index + 1, (const uint64*)NULL, (rank_type*)NULL, (uint64*)NULL); });
             rank_type* ranges = m_mem_ranges.reserve(total);
             uint64*    slots  = m_slots.reserve(total);
             if (total)
@@ -640,6 +630,20 @@ private:
         fmindex::check(hipcub::DeviceScan::InclusiveSum(nullptr, tb, values, values, int(n), m_stream), "hipcub::DeviceScan::InclusiveSum");
         uint8* temp = m_temp.reserve(tb + 16u);
         fmindex::check(hipcub::DeviceScan::InclusiveSum(temp, tb, values, values, int(n), m_stream), "hipcub::DeviceScan::InclusiveSum");
+    }
+    /// one counting pass of a generic rank: `launch` runs a kernel that leaves a count per string in counts[0, n); they are scanned
+    /// in place, and their total comes back
+    template <typename launch_type>
+    uint64 count_pass(uint64* counts, const uint32 n, const char* kernel, launch_type launch)
+    {
+        launch();
+        fmindex::check(hipGetLastError(), kernel);
+        scan(counts, n);
+        uint64 total = 0;
+        fmindex::check(hipMemcpyAsync(&total, counts + (n - 1u), sizeof(uint64), hipMemcpyDeviceToHost, m_stream), "hipMemcpyAsync");
+        fmindex::check(hipStreamSynchronize(m_stream), "hipStreamSynchronize");
+        if (total > 0x7FFFFFFFull) throw std::runtime_error("MEMFilter::rank: more than 2^31 - 1 MEMs in one call");
+        return total;
     }
     template <typename string_set_type>
     bool rank_tuned(const string_set_type&, const uint32, const uint32, const uint32, const uint32, const uint32, const uint32, std::false_type) { return false; }

@@ -19,7 +19,12 @@
 //
 // rank is two passes of the same walk: the first counts the reported MEMs of every string, a scan turns the counts into the
 // exclusive index, the second writes each record to its place.  Nothing is written past `capacity`.
+//
+// The plain and the re-seeding entry differ in their kernels and in what follows the first pass.  What they share is written once:
+// the argument checks (mem_rank_admission, fm_mem_args.h, with the `_host` twins), the temp layout (MemTemp: mem_temp_carve places
+// it, and the size queries ask the same function), the first pass (mem_count_pass) and a lane's view of its string (mem_lane_string).
 #include "fm_bidir.h"
+#include "fm_mem_args.h"
 #include <hipcub/hipcub.hpp>
 
 namespace nvb {
@@ -94,6 +99,21 @@ __device__ __forceinline__ uint32_t mem_group(const Fmi& f, const Fmi& r, const 
     return (m != 0u && i > x + 1u) ? i : x + 1u;
 }
 
+// what a lane walks of string id: where it begins, and its length.  A string longer than max_len is refused by the entry -- the
+// counting pass raises the flag for it -- and walked up to max_len, which is what the store has room for.
+template <bool EMIT>
+__device__ __forceinline__ uint32_t mem_lane_string(const StringSet& strings, const uint64_t id, const uint32_t max_len, uint32_t* const too_long, uint64_t& pbegin)
+{
+    pbegin = strings.begin[id];
+    uint32_t len = strings.length ? strings.length[id] : strings.fixed_length;
+    if (len > max_len)
+    {
+        if (!EMIT) *too_long = 1u;
+        len = max_len;
+    }
+    return len;
+}
+
 template <bool EMIT>
 __global__ void __launch_bounds__(256)
 fm_mem_kernel(const Fmi f, const Fmi r, const StringSet strings, const uint32_t n, const uint32_t max_len,
@@ -105,13 +125,8 @@ fm_mem_kernel(const Fmi f, const Fmi r, const StringSet strings, const uint32_t 
     uint32_t* const st  = store + size_t(tid >> 6) * max_len * 192u + (tid & 63u);        // entry j, word w: st[(j * 3 + w) * 64]
     for (uint64_t id = tid; id < n; id += uint64_t(gridDim.x) * 256u)
     {
-        const uint64_t pbegin = strings.begin[id];
-        uint32_t len = strings.length ? strings.length[id] : strings.fixed_length;
-        if (len > max_len)                             // refused by the entry; the store has room for max_len entries
-        {
-            if (!EMIT) *too_long = 1u;
-            len = max_len;
-        }
+        uint64_t pbegin;
+        const uint32_t len = mem_lane_string<EMIT>(strings, id, max_len, too_long, pbegin);
         const uint64_t base = EMIT ? index[id] : 0ull;
         uint32_t count = 0;
         PatternCursor pc; pc.g0 = 0xFFFFFFFFu; pc.grp = 0;
@@ -161,13 +176,8 @@ fm_mem_split_kernel(const Fmi f, const Fmi r, const StringSet strings, const uin
     uint32_t* const st2 = st + size_t(max_len) * 192u;
     for (uint64_t id = tid; id < n; id += uint64_t(gridDim.x) * 256u)
     {
-        const uint64_t pbegin = strings.begin[id];
-        uint32_t len = strings.length ? strings.length[id] : strings.fixed_length;
-        if (len > max_len)                             // refused by the entry; the store has room for max_len entries
-        {
-            if (!EMIT) *too_long = 1u;
-            len = max_len;
-        }
+        uint64_t pbegin;
+        const uint32_t len = mem_lane_string<EMIT>(strings, id, max_len, too_long, pbegin);
         uint4* const seg = EMIT ? staging + raw_index[id] : nullptr;       // room for every span counted by the first pass
         uint32_t raw = 0, kept = 0;
         PatternCursor pc; pc.g0 = 0xFFFFFFFFu; pc.grp = 0;
@@ -258,24 +268,65 @@ fm_extend_kernel(const int32_t direction, const Fmi f, const Fmi r, const uint2*
 
 static inline uint64_t mem_align256(uint64_t x) { return (x + 255ull) & ~255ull; }
 static inline uint32_t mem_blocks(uint32_t n) { const uint64_t b = (uint64_t(n) + 255u) / 256u; return uint32_t(b < MEM_MAX_BLOCKS ? b : MEM_MAX_BLOCKS); }
-static inline uint64_t mem_store_bytes(uint32_t n, uint32_t max_len) { return mem_align256(uint64_t(mem_blocks(n)) * 256u * max_len * 12u); }
-static inline uint64_t mem_counts_bytes(uint32_t n) { return mem_align256(uint64_t(n) * 8u) + 256u; }      // the counts, then the too-long flag
-static inline uint64_t mem_scan_bytes(uint32_t n, uint32_t max_len)
+
+// The temp of a rank entry, in this order.  The plain entry (split == false) has neither raw_index nor staging, and half the store.
+struct MemTemp {
+    uint32_t* store;        // the kept ranges of the lanes in flight: max_len entries a lane, and as many again for the re-seeds
+    uint64_t* counts;       // n counts (split: before, then after, the duplicates go), then 256 bytes that hold
+    uint32_t* too_long;     //   the flag of a string longer than max_len
+    uint64_t* raw_index;    // split: the n + 1 segment bounds of the staging table
+    void*     scan;         // hipCUB's: n counts, then the sizes of the stored records
+    size_t    scan_bytes;
+    uint4*    staging;      // split: at most `capacity` records (never more than 2^31 - 1)
+    uint64_t  bytes;        // all of it; the split entry runs the plain one for the no-split sentinel, so never less than the plain layout
+};
+// a null `temp` gives the sizes alone
+static MemTemp mem_temp_carve(void* temp, const uint32_t n, const uint32_t max_len, const bool split, const uint64_t capacity)
 {
-    const uint64_t most = std::max<uint64_t>(std::min<uint64_t>(uint64_t(n) * max_len, 0x7FFFFFFFull), n);
+    const uint64_t staged = std::min<uint64_t>(capacity, 0x7FFFFFFFull);
+    const uint64_t most   = split ? std::max<uint64_t>(staged, n) : std::max<uint64_t>(std::min<uint64_t>(uint64_t(n) * max_len, 0x7FFFFFFFull), n);
     size_t scan = 0;
     (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan, (const uint64_t*)nullptr, (uint64_t*)nullptr, int(most));      // size query only
-    return mem_align256(scan) + 256u;
+
+    uintptr_t p = reinterpret_cast<uintptr_t>(temp);
+    auto take = [&p](const uint64_t bytes) { const uintptr_t at = p; p += bytes; return at; };
+    MemTemp t;
+    t.store      = reinterpret_cast<uint32_t*>(take((split ? 2u : 1u) * mem_align256(uint64_t(mem_blocks(n)) * 256u * max_len * 12u)));
+    t.counts     = reinterpret_cast<uint64_t*>(take(mem_align256(uint64_t(n) * 8u) + 256u));
+    t.too_long   = reinterpret_cast<uint32_t*>(p - 256u);
+    t.raw_index  = reinterpret_cast<uint64_t*>(take(split ? mem_align256((uint64_t(n) + 1u) * 8u) : 0u));
+    t.scan_bytes = size_t(mem_align256(scan) + 256u);
+    t.scan       = reinterpret_cast<void*>(take(t.scan_bytes));
+    t.staging    = reinterpret_cast<uint4*>(take(split ? mem_align256(staged * 16u) : 0u));
+    t.bytes      = uint64_t(p - reinterpret_cast<uintptr_t>(temp));
+    if (split) t.bytes = std::max<uint64_t>(t.bytes, mem_temp_carve(nullptr, n, max_len, false, 0u).bytes);
+    return t;
 }
-// the split entry scans n counts and at most `capacity` sizes, and stages at most `capacity` records (never more than 2^31 - 1)
-static inline uint64_t mem_split_staged(uint64_t capacity) { return std::min<uint64_t>(capacity, 0x7FFFFFFFull); }
-static inline uint64_t mem_split_scan_bytes(uint32_t n, uint64_t capacity)
+// what the size queries answer: 256 for a shape the entries refuse or have nothing to do for
+static uint64_t mem_temp_bytes(const uint32_t n, const uint32_t max_len, const bool split, const uint64_t capacity)
 {
-    size_t scan = 0;
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan, (const uint64_t*)nullptr, (uint64_t*)nullptr, int(std::max<uint64_t>(mem_split_staged(capacity), n)));
-    return mem_align256(scan) + 256u;
+    if (n == 0 || max_len == 0 || max_len > 65535u || n >= 0x80000000u) return 256u;
+    return mem_temp_carve(nullptr, n, max_len, split, capacity).bytes;
 }
-static inline uint64_t mem_split_index_bytes(uint32_t n) { return mem_align256((uint64_t(n) + 1u) * 8u); }
+
+// The first pass of both entries: count() launches the <false> kernel on t.counts and t.too_long, the counts are scanned into
+// index + 1, and the total comes back with the flag.  Synchronises the stream; refuses a batch that holds a string longer than
+// max_pattern_len.
+template <typename Count>
+static int mem_count_pass(MemTemp& t, const uint32_t n, uint64_t* out_index, uint64_t* index, hipStream_t s, Count&& count, uint64_t& total)
+{
+    if (hipError_t e = hipMemsetAsync(out_index, 0, 8u, s)) return e;
+    if (index != out_index) if (hipError_t e = hipMemsetAsync(index, 0, 8u, s)) return e;
+    if (hipError_t e = hipMemsetAsync(t.too_long, 0, 4u, s)) return e;
+    count();
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(t.scan, t.scan_bytes, t.counts, index + 1, int(n), s)) return e;
+    uint32_t refused = 0;
+    if (hipError_t e = hipMemcpyAsync(&total, index + n, 8u, hipMemcpyDeviceToHost, s)) return e;
+    if (hipError_t e = hipMemcpyAsync(&refused, t.too_long, 4u, hipMemcpyDeviceToHost, s)) return e;
+    if (hipError_t e = hipStreamSynchronize(s)) return e;
+    return refused ? hipErrorInvalidValue : hipSuccess;
+}
 
 } // namespace nvb
 
@@ -302,76 +353,42 @@ NVB_API int nvbio_hip_fm_extend(int32_t direction, const nvbio_hip_fmindex* f_fm
     return hipGetLastError();
 }
 
-NVB_API uint64_t nvbio_hip_fm_mem_temp_bytes(uint32_t n, uint32_t max_pattern_len)
-{
-    if (n == 0 || max_pattern_len == 0 || max_pattern_len > 65535u || n >= 0x80000000u) return 256u;
-    return mem_store_bytes(n, max_pattern_len) + mem_counts_bytes(n) + mem_scan_bytes(n, max_pattern_len);
-}
+NVB_API uint64_t nvbio_hip_fm_mem_temp_bytes(uint32_t n, uint32_t max_pattern_len) { return mem_temp_bytes(n, max_pattern_len, false, 0u); }
 
 NVB_API int nvbio_hip_fm_mem_rank(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
                                   uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
                                   uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
                                   void* temp, uint64_t temp_bytes, void* stream)
 {
-    if (int e = check_bidir(f_fmi, r_fmi)) return e;
-    if (!out_index || !out_n_ranges || min_intv == 0u) return hipErrorInvalidValue;
-    if (n >= 0x80000000u || max_pattern_len > 65535u) return hipErrorInvalidValue;
-    if (capacity != 0u && (!out_ranges || !out_slots)) return hipErrorInvalidValue;
     hipStream_t s = to_stream(stream);
-    *out_n_ranges = 0;
-    if (n == 0 || max_pattern_len == 0)
-    {
-        // no string has a symbol: an index of zeros
-        return hipMemsetAsync(out_index, 0, (uint64_t(n) + 1u) * 8u, s);
-    }
-    if (!strings || !strings->words || !strings->begin || strings->n_words == 0) return hipErrorInvalidValue;
-    if (!(strings->bits == 2 || strings->bits == 4)) return hipErrorNotSupported;
-    if (!strings->length && strings->fixed_length > max_pattern_len) return hipErrorInvalidValue;
-    if (!temp || temp_bytes < nvbio_hip_fm_mem_temp_bytes(n, max_pattern_len)) return hipErrorInvalidValue;
-
-    uint8_t*  p       = reinterpret_cast<uint8_t*>(temp);
-    uint32_t* store   = reinterpret_cast<uint32_t*>(p);                 p += mem_store_bytes(n, max_pattern_len);
-    uint64_t* counts  = reinterpret_cast<uint64_t*>(p);                 p += mem_counts_bytes(n);
-    uint32_t* too_long = reinterpret_cast<uint32_t*>(p - 256);
-    void*     scan    = p;
-    size_t scan_bytes = size_t(temp_bytes - uint64_t(p - reinterpret_cast<uint8_t*>(temp)));
+    const int admitted = mem_rank_admission(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, out_ranges, capacity, out_index, out_slots, out_n_ranges, [] {});
+    if (admitted == MEM_ARGS_EMPTY) return hipMemsetAsync(out_index, 0, (uint64_t(n) + 1u) * 8u, s);
+    if (admitted != MEM_ARGS_GO) return admitted;
+    MemTemp t = mem_temp_carve(temp, n, max_pattern_len, false, 0u);
+    if (!temp || temp_bytes < t.bytes) return hipErrorInvalidValue;
     const dim3 grid(mem_blocks(n)), block(256);
     const Fmi f = make_fmi(f_fmi), r = make_fmi(r_fmi);
     const StringSet set = make_string_set(strings);
 
-    if (hipError_t e = hipMemsetAsync(out_index, 0, 8u, s)) return e;
-    if (hipError_t e = hipMemsetAsync(too_long, 0, 4u, s)) return e;
     g_last_kernel = "fm_mem_kernel";
-    hipLaunchKernelGGL(fm_mem_kernel<false>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span,
-                       store, counts, (const uint64_t*)nullptr, (uint4*)nullptr, (uint64_t*)nullptr, 0ull, too_long);
-    if (hipError_t e = hipGetLastError()) return e;
-    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, counts, out_index + 1, int(n), s)) return e;
     uint64_t total = 0;
-    uint32_t refused = 0;
-    if (hipError_t e = hipMemcpyAsync(&total, out_index + n, 8u, hipMemcpyDeviceToHost, s)) return e;
-    if (hipError_t e = hipMemcpyAsync(&refused, too_long, 4u, hipMemcpyDeviceToHost, s)) return e;
-    if (hipError_t e = hipStreamSynchronize(s)) return e;
-    if (refused) return hipErrorInvalidValue;                          // a string longer than max_pattern_len
+    if (int e = mem_count_pass(t, n, out_index, out_index, s, [&] {
+            hipLaunchKernelGGL(fm_mem_kernel<false>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span,
+                               t.store, t.counts, (const uint64_t*)nullptr, (uint4*)nullptr, (uint64_t*)nullptr, 0ull, t.too_long); }, total)) return e;
     *out_n_ranges = total;
     const uint64_t stored = total < capacity ? total : capacity;
     if (stored > 0x7FFFFFFFull) return hipErrorInvalidValue;           // the scan below counts in 31 bits
     if (stored)
     {
         hipLaunchKernelGGL(fm_mem_kernel<true>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span,
-                           store, counts, out_index, reinterpret_cast<uint4*>(out_ranges), out_slots, capacity, (uint32_t*)nullptr);
+                           t.store, t.counts, out_index, reinterpret_cast<uint4*>(out_ranges), out_slots, capacity, (uint32_t*)nullptr);
         if (hipError_t e = hipGetLastError()) return e;
-        if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, out_slots, out_slots, int(stored), s)) return e;
+        if (hipError_t e = hipcub::DeviceScan::InclusiveSum(t.scan, t.scan_bytes, out_slots, out_slots, int(stored), s)) return e;
     }
     return total > capacity ? NVBIO_HIP_ERROR_CAPACITY : hipSuccess;
 }
 
-NVB_API uint64_t nvbio_hip_fm_mem_split_temp_bytes(uint32_t n, uint32_t max_pattern_len, uint64_t capacity)
-{
-    if (n == 0 || max_pattern_len == 0 || max_pattern_len > 65535u || n >= 0x80000000u) return 256u;
-    const uint64_t split = 2u * mem_store_bytes(n, max_pattern_len) + mem_counts_bytes(n) + mem_split_index_bytes(n) +
-                           mem_split_scan_bytes(n, capacity) + mem_align256(mem_split_staged(capacity) * 16u);
-    return std::max<uint64_t>(split, nvbio_hip_fm_mem_temp_bytes(n, max_pattern_len));        // the no-split sentinel runs the plain entry
-}
+NVB_API uint64_t nvbio_hip_fm_mem_split_temp_bytes(uint32_t n, uint32_t max_pattern_len, uint64_t capacity) { return mem_temp_bytes(n, max_pattern_len, true, capacity); }
 
 NVB_API int nvbio_hip_fm_mem_rank_split(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
                                         uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
@@ -382,58 +399,35 @@ NVB_API int nvbio_hip_fm_mem_rank_split(const nvbio_hip_fmindex* f_fmi, const nv
     if (split_len == 0xFFFFFFFFu)                      // no re-seeding: the plain entry, word for word
         return nvbio_hip_fm_mem_rank(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, max_intv, min_span, out_ranges, capacity, out_index, out_slots,
                                      out_n_ranges, temp, temp_bytes, stream);
-    if (int e = check_bidir(f_fmi, r_fmi)) return e;
-    if (!out_index || !out_n_ranges || min_intv == 0u) return hipErrorInvalidValue;
-    if (n >= 0x80000000u || max_pattern_len > 65535u) return hipErrorInvalidValue;
-    if (capacity != 0u && (!out_ranges || !out_slots)) return hipErrorInvalidValue;
     hipStream_t s = to_stream(stream);
-    *out_n_ranges = 0;
-    if (n == 0 || max_pattern_len == 0) return hipMemsetAsync(out_index, 0, (uint64_t(n) + 1u) * 8u, s);
-    if (!strings || !strings->words || !strings->begin || strings->n_words == 0) return hipErrorInvalidValue;
-    if (!(strings->bits == 2 || strings->bits == 4)) return hipErrorNotSupported;
-    if (!strings->length && strings->fixed_length > max_pattern_len) return hipErrorInvalidValue;
-    if (!temp || temp_bytes < nvbio_hip_fm_mem_split_temp_bytes(n, max_pattern_len, capacity)) return hipErrorInvalidValue;
-
-    uint8_t*  p         = reinterpret_cast<uint8_t*>(temp);
-    uint32_t* store     = reinterpret_cast<uint32_t*>(p);               p += 2u * mem_store_bytes(n, max_pattern_len);
-    uint64_t* counts    = reinterpret_cast<uint64_t*>(p);               p += mem_counts_bytes(n);       // before, then after, duplicates go
-    uint32_t* too_long  = reinterpret_cast<uint32_t*>(p - 256);
-    uint64_t* raw_index = reinterpret_cast<uint64_t*>(p);               p += mem_split_index_bytes(n);
-    void*     scan      = p;                                            p += mem_split_scan_bytes(n, capacity);
-    size_t scan_bytes   = size_t(mem_split_scan_bytes(n, capacity));
-    uint4*    staging   = reinterpret_cast<uint4*>(p);
+    const int admitted = mem_rank_admission(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, out_ranges, capacity, out_index, out_slots, out_n_ranges, [] {});
+    if (admitted == MEM_ARGS_EMPTY) return hipMemsetAsync(out_index, 0, (uint64_t(n) + 1u) * 8u, s);
+    if (admitted != MEM_ARGS_GO) return admitted;
+    MemTemp t = mem_temp_carve(temp, n, max_pattern_len, true, capacity);
+    if (!temp || temp_bytes < t.bytes) return hipErrorInvalidValue;
     const dim3 grid(mem_blocks(n)), block(256);
     const Fmi f = make_fmi(f_fmi), r = make_fmi(r_fmi);
     const StringSet set = make_string_set(strings);
 
-    if (hipError_t e = hipMemsetAsync(out_index, 0, 8u, s)) return e;
-    if (hipError_t e = hipMemsetAsync(raw_index, 0, 8u, s)) return e;
-    if (hipError_t e = hipMemsetAsync(too_long, 0, 4u, s)) return e;
     g_last_kernel = "fm_mem_split_kernel";
-    hipLaunchKernelGGL(fm_mem_split_kernel<false>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span, split_len, split_width,
-                       store, counts, (const uint64_t*)nullptr, (uint4*)nullptr, (uint64_t*)nullptr, too_long);
-    if (hipError_t e = hipGetLastError()) return e;
-    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, counts, raw_index + 1, int(n), s)) return e;
     uint64_t raw = 0, total = 0;
-    uint32_t refused = 0;
-    if (hipError_t e = hipMemcpyAsync(&raw, raw_index + n, 8u, hipMemcpyDeviceToHost, s)) return e;
-    if (hipError_t e = hipMemcpyAsync(&refused, too_long, 4u, hipMemcpyDeviceToHost, s)) return e;
-    if (hipError_t e = hipStreamSynchronize(s)) return e;
-    if (refused) return hipErrorInvalidValue;                          // a string longer than max_pattern_len
+    if (int e = mem_count_pass(t, n, out_index, t.raw_index, s, [&] {
+            hipLaunchKernelGGL(fm_mem_split_kernel<false>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span, split_len, split_width,
+                               t.store, t.counts, (const uint64_t*)nullptr, (uint4*)nullptr, (uint64_t*)nullptr, t.too_long); }, raw)) return e;
     if (raw > capacity) { *out_n_ranges = raw; return NVBIO_HIP_ERROR_CAPACITY; }       // the staging table has room for `capacity` spans
     if (raw > 0x7FFFFFFFull) return hipErrorInvalidValue;              // the scans count in 31 bits
     if (raw == 0) return hipMemsetAsync(out_index, 0, (uint64_t(n) + 1u) * 8u, s);
 
     hipLaunchKernelGGL(fm_mem_split_kernel<true>, grid, block, 0, s, f, r, set, n, max_pattern_len, min_intv, max_intv, min_span, split_len, split_width,
-                       store, (uint64_t*)nullptr, raw_index, staging, counts, (uint32_t*)nullptr);
+                       t.store, (uint64_t*)nullptr, t.raw_index, t.staging, t.counts, (uint32_t*)nullptr);
     if (hipError_t e = hipGetLastError()) return e;
-    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, counts, out_index + 1, int(n), s)) return e;
-    hipLaunchKernelGGL(fm_mem_compact_kernel, dim3(uint32_t((raw + 255u) / 256u)), block, 0, s, staging, raw_index, out_index, raw,
+    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(t.scan, t.scan_bytes, t.counts, out_index + 1, int(n), s)) return e;
+    hipLaunchKernelGGL(fm_mem_compact_kernel, dim3(uint32_t((raw + 255u) / 256u)), block, 0, s, t.staging, t.raw_index, out_index, raw,
                        reinterpret_cast<uint4*>(out_ranges), out_slots);
     if (hipError_t e = hipGetLastError()) return e;
     if (hipError_t e = hipMemcpyAsync(&total, out_index + n, 8u, hipMemcpyDeviceToHost, s)) return e;
     if (hipError_t e = hipStreamSynchronize(s)) return e;
-    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(scan, scan_bytes, out_slots, out_slots, int(total), s)) return e;
+    if (hipError_t e = hipcub::DeviceScan::InclusiveSum(t.scan, t.scan_bytes, out_slots, out_slots, int(total), s)) return e;
     *out_n_ranges = total;
     return hipSuccess;
 }

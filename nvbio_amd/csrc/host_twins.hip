@@ -6,6 +6,7 @@
 // strings.  These are explicit entry points -- nothing in the device path ever falls back to them.
 #define NVBIO_HIP_COMPAT_NO_TUNED 1
 #include "common.h"
+#include "fm_mem_args.h"
 #include "../../include/nvbio_hip/compat/nvbio/alignment/alignment.h"
 #include "../../include/nvbio_hip/compat/nvbio/fmindex/fmindex.h"
 #include "../../include/nvbio_hip/compat/nvbio/fmindex/mem.h"
@@ -298,76 +299,22 @@ NVB_API int nvbio_hip_fm_extend_host(int32_t direction, const nvbio_hip_fmindex*
     return hipSuccess;
 }
 
-NVB_API int nvbio_hip_fm_mem_rank_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
-                                       uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
-                                       uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
-                                       uint64_t* out_records, int32_t n_threads)
-{
-    if (!f_fmi || !r_fmi || !f_fmi->bwt_occ || !r_fmi->bwt_occ || f_fmi->length != r_fmi->length) return hipErrorInvalidValue;
-    if (!out_index || !out_n_ranges || min_intv == 0u) return hipErrorInvalidValue;
-    if (n >= 0x80000000u || max_pattern_len > 65535u) return hipErrorInvalidValue;
-    if (capacity != 0u && (!out_ranges || !out_slots)) return hipErrorInvalidValue;
-    *out_n_ranges = 0;
-    if (out_records) *out_records = 0;
-    out_index[0] = 0;
-    if (n == 0 || max_pattern_len == 0) { for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = 0; return hipSuccess; }
-    if (!strings || !strings->words || !strings->begin || strings->n_words == 0) return hipErrorInvalidValue;
-    if (!(strings->bits == 2 || strings->bits == 4)) return hipErrorNotSupported;
-    if (!strings->length && strings->fixed_length > max_pattern_len) return hipErrorInvalidValue;
-    if (strings->length) for (uint32 i = 0; i < n; ++i) if (strings->length[i] > max_pattern_len) return hipErrorInvalidValue;
-    const fmi_t f = host_index(f_fmi), r = host_index(r_fmi);
-#if defined(_OPENMP)
-    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
-#endif
-    std::vector< std::vector< MEMRange<uint32> > > found(n);
-    uint64 records = 0;
-    #pragma omp parallel num_threads(threads) reduction(+ : records)
-    {
-        std::vector<uint4> store;
-        #pragma omp for schedule(dynamic, 256)
-        for (int64 i = 0; i < int64(n); ++i)
-        {
-            const RtString s = string_of(strings, uint32(i));
-            const uint32 len = s.len < max_pattern_len ? s.len : max_pattern_len;
-            fmindex::string_mems(s, len, uint32(i), f, r, min_intv, max_intv, min_span, found[i], store, &records);
-        }
-    }
-    for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = out_index[i] + found[i].size();
-    uint64 sum = 0;
-    for (uint32 i = 0; i < n; ++i)
-        for (size_t k = 0; k < found[i].size(); ++k)
-        {
-            const uint64 at = out_index[i] + k;
-            if (at >= capacity) break;
-            const uint4 v = found[i][k].coords;
-            out_ranges[4 * at] = v.x; out_ranges[4 * at + 1] = v.y; out_ranges[4 * at + 2] = v.z; out_ranges[4 * at + 3] = v.w;
-            sum += uint64(found[i][k].range_size()); out_slots[at] = sum;
-        }
-    *out_n_ranges = out_index[n];
-    if (out_records) *out_records = records;
-    return out_index[n] > capacity ? NVBIO_HIP_ERROR_CAPACITY : int(hipSuccess);
-}
+namespace {
 
-NVB_API int nvbio_hip_fm_mem_rank_split_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
-                                             uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
-                                             uint32_t split_len, uint32_t split_width,
-                                             uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
-                                             uint64_t* out_records, int32_t n_threads)
+// The body of both rank twins.  walk(string, length, id, f, r, out, store, store2, &records) appends a string's records to `out` and
+// returns how many spans it found.  What happens when `capacity` is too small follows the device entries: the plain one stores the
+// first `capacity` records and reports the total; the re-seeding one (store_nothing) stages every span found, duplicates
+// included, so past that many it stores nothing and reports that count.
+template <typename Walk>
+int mem_rank_twin(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                  const uint32 n, const uint32 max_pattern_len, const uint32 min_intv,
+                  uint32* out_ranges, const uint64 capacity, uint64* out_index, uint64* out_slots, uint64* out_n_ranges,
+                  uint64* out_records, const int32 n_threads, const bool store_nothing, const Walk walk)
 {
-    if (split_len == 0xFFFFFFFFu)                      // no re-seeding: the plain twin, word for word
-        return nvbio_hip_fm_mem_rank_host(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, max_intv, min_span, out_ranges, capacity, out_index, out_slots,
-                                          out_n_ranges, out_records, n_threads);
-    if (!f_fmi || !r_fmi || !f_fmi->bwt_occ || !r_fmi->bwt_occ || f_fmi->length != r_fmi->length) return hipErrorInvalidValue;
-    if (!out_index || !out_n_ranges || min_intv == 0u) return hipErrorInvalidValue;
-    if (n >= 0x80000000u || max_pattern_len > 65535u) return hipErrorInvalidValue;
-    if (capacity != 0u && (!out_ranges || !out_slots)) return hipErrorInvalidValue;
-    *out_n_ranges = 0;
-    if (out_records) *out_records = 0;
-    out_index[0] = 0;
-    if (n == 0 || max_pattern_len == 0) { for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = 0; return hipSuccess; }
-    if (!strings || !strings->words || !strings->begin || strings->n_words == 0) return hipErrorInvalidValue;
-    if (!(strings->bits == 2 || strings->bits == 4)) return hipErrorNotSupported;
-    if (!strings->length && strings->fixed_length > max_pattern_len) return hipErrorInvalidValue;
+    const int admitted = nvb::mem_rank_admission(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, out_ranges, capacity, out_index, out_slots, out_n_ranges,
+                                                 [=]() { if (out_records) *out_records = 0; out_index[0] = 0; });
+    if (admitted != nvb::MEM_ARGS_GO && admitted != nvb::MEM_ARGS_EMPTY) return admitted;
+    if (admitted == nvb::MEM_ARGS_EMPTY) { for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = 0; return hipSuccess; }
     if (strings->length) for (uint32 i = 0; i < n; ++i) if (strings->length[i] > max_pattern_len) return hipErrorInvalidValue;
     const fmi_t f = host_index(f_fmi), r = host_index(r_fmi);
 #if defined(_OPENMP)
@@ -383,23 +330,43 @@ NVB_API int nvbio_hip_fm_mem_rank_split_host(const nvbio_hip_fmindex* f_fmi, con
         {
             const RtString s = string_of(strings, uint32(i));
             const uint32 len = s.len < max_pattern_len ? s.len : max_pattern_len;
-            raw += fmindex::string_mems_split(s, len, uint32(i), f, r, min_intv, max_intv, min_span, split_len, split_width, found[i], store, store2, &records);
+            raw += walk(s, len, uint32(i), f, r, found[i], store, store2, &records);
         }
     }
     if (out_records) *out_records = records;
-    if (raw > capacity) { *out_n_ranges = raw; return NVBIO_HIP_ERROR_CAPACITY; }       // the device entry stages every span found: the same rule
-    for (uint32 i = 0; i < n; ++i) out_index[i + 1u] = out_index[i] + found[i].size();
-    uint64 sum = 0;
-    for (uint32 i = 0; i < n; ++i)
-        for (size_t k = 0; k < found[i].size(); ++k)
-        {
-            const uint64 at = out_index[i] + k;
-            const uint4 v = found[i][k].coords;
-            out_ranges[4 * at] = v.x; out_ranges[4 * at + 1] = v.y; out_ranges[4 * at + 2] = v.z; out_ranges[4 * at + 3] = v.w;
-            sum += uint64(found[i][k].range_size()); out_slots[at] = sum;
-        }
+    if (store_nothing && raw > capacity) { *out_n_ranges = raw; return NVBIO_HIP_ERROR_CAPACITY; }
+    fmindex::flatten_mems(found, capacity, out_index, [out_ranges](const uint64 at, const MEMRange<uint32>& m)
+                          { uint32* o = out_ranges + 4 * at; o[0] = m.coords.x; o[1] = m.coords.y; o[2] = m.coords.z; o[3] = m.coords.w; }, out_slots);
     *out_n_ranges = out_index[n];
-    return hipSuccess;
+    return out_index[n] > capacity ? NVBIO_HIP_ERROR_CAPACITY : int(hipSuccess);
+}
+
+} // namespace
+
+NVB_API int nvbio_hip_fm_mem_rank_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                                       uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                                       uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                                       uint64_t* out_records, int32_t n_threads)
+{
+    return mem_rank_twin(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, out_ranges, capacity, out_index, out_slots, out_n_ranges, out_records, n_threads,
+                         false, [=](const RtString& s, const uint32 len, const uint32 id, const fmi_t& f, const fmi_t& r, std::vector< MEMRange<uint32> >& out,
+                                    std::vector<uint4>& store, std::vector<uint4>&, uint64* records)
+                         { fmindex::string_mems(s, len, id, f, r, min_intv, max_intv, min_span, out, store, records); return uint64(out.size()); });
+}
+
+NVB_API int nvbio_hip_fm_mem_rank_split_host(const nvbio_hip_fmindex* f_fmi, const nvbio_hip_fmindex* r_fmi, const nvbio_hip_string_set* strings,
+                                             uint32_t n, uint32_t max_pattern_len, uint32_t min_intv, uint32_t max_intv, uint32_t min_span,
+                                             uint32_t split_len, uint32_t split_width,
+                                             uint32_t* out_ranges, uint64_t capacity, uint64_t* out_index, uint64_t* out_slots, uint64_t* out_n_ranges,
+                                             uint64_t* out_records, int32_t n_threads)
+{
+    if (split_len == 0xFFFFFFFFu)                      // no re-seeding: the plain twin, word for word
+        return nvbio_hip_fm_mem_rank_host(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, max_intv, min_span, out_ranges, capacity, out_index, out_slots,
+                                          out_n_ranges, out_records, n_threads);
+    return mem_rank_twin(f_fmi, r_fmi, strings, n, max_pattern_len, min_intv, out_ranges, capacity, out_index, out_slots, out_n_ranges, out_records, n_threads,
+                         true, [=](const RtString& s, const uint32 len, const uint32 id, const fmi_t& f, const fmi_t& r, std::vector< MEMRange<uint32> >& out,
+                                   std::vector<uint4>& store, std::vector<uint4>& store2, uint64* records)
+                         { return fmindex::string_mems_split(s, len, id, f, r, min_intv, max_intv, min_span, split_len, split_width, out, store, store2, records); });
 }
 
 NVB_API int nvbio_hip_fm_mem_locate_host(const nvbio_hip_fmindex* f_fmi, const uint32_t* ranges, const uint64_t* slots, uint64_t n_ranges,
@@ -417,8 +384,7 @@ NVB_API int nvbio_hip_fm_mem_locate_host(const nvbio_hip_fmindex* f_fmi, const u
     for (int64 h = 0; h < int64(end - begin); ++h)
     {
         const uint64 g = begin + uint64(h);
-        uint64 lo = 0, hi = n_ranges;
-        while (lo < hi) { const uint64 mid = lo + (hi - lo) / 2u; if (slots[mid] <= g) lo = mid + 1u; else hi = mid; }
+        const uint64 lo = nvbio::upper_bound_index(g, slots, n_ranges);
         uint32* o = out_hits + 4 * h;
         if (lo >= n_ranges) { o[0] = o[1] = 0xFFFFFFFFu; o[2] = o[3] = 0u; continue; }
         const uint32* rg = ranges + 4 * lo;
