@@ -54,6 +54,7 @@ thread_local const char* g_last_pair_cell = "";
 thread_local const char* g_last_pair_fetch = "";
 thread_local const char* g_last_pair_frame = "";
 thread_local const char* g_last_pair_row = "";
+thread_local const char* g_last_pair_const = "";
 
 #define NVB_DECL(B) \
     extern template hipError_t launch_band_width<B, NoQual>(const GotohParams&, const NoQual&, int, bool, hipStream_t); \
@@ -75,6 +76,11 @@ NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
     extern template hipError_t launch_band_pair<15, PD3, (F)>(const GotohParams&, hipStream_t); \
     extern template hipError_t launch_band_pair<15, PD3, (F) | PF_ROW2>(const GotohParams&, hipStream_t);
 NVB_DECL(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_DECL)
+#undef NVB_DECL
+#define NVB_DECL(F) extern template hipError_t launch_band_pair<15, PD3, (F)>(const GotohParams&, hipStream_t);
+#define NVB_DECL_GE(F) NVB_PAIR_GE_FORMS(NVB_DECL, F)
+NVB_DECL_GE(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_DECL_GE)
+#undef NVB_DECL_GE
 #undef NVB_DECL
 
 template <typename QA>
@@ -165,11 +171,13 @@ static bool pair_stream_admitted(const GotohParams& p)
     return p.pat.s.bits != 8u && p.pat.s.n_words <= (1ull << 29) && p.txt.s.n_words <= (1ull << 29);
 }
 // ROW: PF_ROW2 for the column frame's cell (its sink folded once per two rows), 0 for the row as it was, which the row-frame cells
-// keep and NVBIO_HIP_PAIR_ROW = 1 asks for.  nvbio_hip_last_kernel_row() says which one ran.
+// keep and NVBIO_HIP_PAIR_ROW = 1 asks for.  nvbio_hip_last_kernel_row() says which one ran.  With PF_ROW2, ROW also carries the
+// constants' placement (launch_pair), which nvbio_hip_last_kernel_const() reports.
 template <typename CELL, int ROW>
 static hipError_t launch_pair_row(const GotohParams& p, hipStream_t s)
 {
-    g_last_pair_row = ROW ? "fold2" : "plain";
+    g_last_pair_row = (ROW & PF_ROW2) ? "fold2" : "plain";
+    g_last_pair_const = (ROW & PF_KLIT) ? "literal" : "scalar";
     g_last_pair_fetch = "generic";
     if (!pair_stream_admitted(p)) return launch_band_pair<15, CELL, PF_SINK_VCC | ROW>(p, s);
     g_last_pair_fetch = "stream";
@@ -183,7 +191,22 @@ static hipError_t launch_pair_row(const GotohParams& p, hipStream_t s)
 template <typename CELL>
 static hipError_t launch_pair(const GotohParams& p, hipStream_t s)
 {
-    if constexpr (CELL::COLUMN) { if (test_switch(SW_PAIR_ROW) != 1) return launch_pair_row<CELL, PF_ROW2>(p, s); }
+    if constexpr (CELL::COLUMN)
+    {
+        if (test_switch(SW_PAIR_ROW) != 1)
+        {
+            // the cell's key constants K_j and the pair fold's 2 G as literals (banded_gotoh_pair.h, "Where the constants live"): one
+            // instance per |G_e|.  NVBIO_HIP_PAIR_CONST = 1 keeps them in scalar registers, as a |G_e| above 3 does
+            if (test_switch(SW_PAIR_CONST) != 1)
+                switch (p.gap_ext) {
+                case  0: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2>(p, s);
+                case -1: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_GE1>(p, s);
+                case -2: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_GE2>(p, s);
+                case -3: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_GE3>(p, s);
+                }
+            return launch_pair_row<CELL, PF_ROW2>(p, s);
+        }
+    }
     return launch_pair_row<CELL, 0>(p, s);
 }
 
@@ -228,6 +251,7 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
     g_last_pair_fetch = "";
     g_last_pair_frame = "";
     g_last_pair_row = "";
+    g_last_pair_const = "";
     // NVBIO_HIP_FORCE_32BIT=1 disables the 16-bit kernels (used by the tests to cover both widths)
     // the row-frame kernels' limit (the plain launch); the limit of the recurrence as written (asymmetric costs, the bounded form -- and LOCAL jobs
     // between the two limits, which the plain launch hands to the A16P instance)
@@ -703,7 +727,7 @@ namespace nvb {
 static std::atomic<int> g_switch[SW_COUNT];
 static const char* const g_switch_name[SW_COUNT] = { "NVBIO_HIP_FORCE_32BIT", "NVBIO_HIP_NO_STAGING", "NVBIO_HIP_FULL_GENERIC", "NVBIO_HIP_ED_SWEEP",
                                                      "NVBIO_HIP_FULL_SINGLE_JOB", "NVBIO_HIP_FULL_ROWS", "NVBIO_HIP_TRACEBACK_LANES", "NVBIO_HIP_SELECT_LANES",
-                                                     "NVBIO_HIP_BANDED_PAIR", "NVBIO_HIP_PAIR_ROW" };
+                                                     "NVBIO_HIP_BANDED_PAIR", "NVBIO_HIP_PAIR_ROW", "NVBIO_HIP_PAIR_CONST" };
 static void seed_switches()
 {
     static std::once_flag once;
@@ -758,4 +782,5 @@ NVB_API const char* nvbio_hip_last_kernel_detail(void) { return (nvb::g_last_pai
 NVB_API const char* nvbio_hip_last_kernel_fetch(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_fetch : ""; }
 NVB_API const char* nvbio_hip_last_kernel_frame(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_frame : ""; }
 NVB_API const char* nvbio_hip_last_kernel_row(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_row : ""; }
+NVB_API const char* nvbio_hip_last_kernel_const(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_const : ""; }
 NVB_API const char* nvbio_hip_last_kernel_cell(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_cell : ""; }

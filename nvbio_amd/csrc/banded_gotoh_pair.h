@@ -100,6 +100,17 @@
 //     its pair's even row (q = rk(M-1) - Z(M-1,14), bit 4 clear), with Z(M-1,14) = BIAS' + G (2 M + 14) worked out once per job.
 //   tests/test_pair_fold2.py holds the arithmetic in numpy.
 //
+// Where the constants live.  D, the K_j and 2 G are wave-uniform; the column frame keeps them in scalar registers.  A v_add_u32 or
+// v_subrev_u32 with a scalar source issues at the rate of the packed ops, about 4.3 cycles, where the same op on vector registers or a
+// literal takes 2.3 (tools/valu_probe.hip, `mix`; profiles/banded_pair/README.md has the figures).  The forms compute the same values
+// from the same operations; only the operand's class changes, so pair_column_admitted and the numpy models do not:
+//   * PF_DV: D in one vector register, pinned as PM3 pins it.  PF_KV: the fifteen K_j in vector registers as well (four waves).
+//   * PF_KLIT: D in a vector register, K_j = j + (14 - j) G and 2 G as 32-bit literals: G = 32 |G_e| is then a template parameter, the
+//     PF_GE bits.  The column frame's byte admits |G_e| <= 3 for every scheme with max(match, mismatch) >= 0.
+//   * PF_PAD: one s_nop behind each of cell2's three groups of simple ops.  Alone none of the three placements gains more than 0.5 %:
+//     a simple op reaches its short issue only where a scalar instruction follows the group.  PF_KLIT | PF_PAD (PF_CONST2) is 5 % faster
+//     than the scalars and is what the library launches with the pair fold; NVBIO_HIP_PAIR_CONST = 1 keeps the scalars.
+//
 // Two forms that did not pay, kept for tools/pair_row_probe.hip alone (profiles/banded_pair/README.md has the figures).  PF_AHEAD
 // issues row R + 1's two table reads at the head of row R, hidden from the compiler in asm (it sinks a load it sees to its use), and
 // waits for them at the head of row R + 1: the same instructions, no exposed LDS round trip -- and no faster, the other four waves
@@ -130,10 +141,22 @@ enum PairForm : int {
     // the column frame's row (the header comment, "The pair fold" and "Two forms that did not pay"):
     PF_FOLD2    = 1024,                                                             //   the sink folds a pair of rows at a time
     PF_AHEAD    = 512,                                                              //   a row's table words are read while the row before runs (probe only)
-    PF_ORDER    = 2048                                                              //   the cells' chain links interleaved with their independent work (probe only)
+    PF_ORDER    = 2048,                                                             //   the cells' chain links interleaved with their independent work (probe only)
+    // where the column frame's cell keeps its wave-uniform constants (the header comment, "Where the constants live"):
+    PF_DV       = 4096,                                                             //   D in a vector register
+    PF_KV       = 8192,                                                             //   D and the fifteen K_j in vector registers (probe only)
+    PF_KLIT     = 16384,                                                            //   D in a vector register, K_j and 2 G as literals: |G_e| is PF_GE's
+    PF_GE1      = 32768, PF_GE2 = 65536, PF_GE3 = PF_GE1 | PF_GE2,                  //   PF_KLIT's |G_e|, 0 ... 3 (pair_ge)
+    PF_PAD      = 131072                                                            //   an s_nop behind each group of simple ops in cell2 (scalars or PF_KLIT)
 };
+constexpr int pair_ge(int form)     { return (form / PF_GE1) & 3; }
+constexpr int pair_ge_bits(int ge)  { return ge * PF_GE1; }
 // the row the library launches for PD3 (banded_gotoh.hip: launch_pair; NVBIO_HIP_PAIR_ROW = 1 keeps the row without it)
 constexpr int PF_ROW2 = PF_FOLD2;
+// the constants' placement the library launches for PD3 with PF_ROW2 (NVBIO_HIP_PAIR_CONST = 1 keeps the scalars): literals, one instance
+// per |G_e| 0 ... 3 (a scheme with a larger |G_e|, which only negative match scores admit, keeps the scalars too)
+constexpr int PF_CONST2 = PF_KLIT | PF_PAD;
+#define NVB_PAIR_GE_FORMS(X, F) X((F) | PF_ROW2 | PF_CONST2) X((F) | PF_ROW2 | PF_CONST2 | PF_GE1) X((F) | PF_ROW2 | PF_CONST2 | PF_GE2) X((F) | PF_ROW2 | PF_CONST2 | PF_GE3)
 // the streamed forms the library holds: every pattern width and byte order it streams
 #define NVB_PAIR_STREAM_FORMS(X) \
     X(PF_STREAM) X(PF_STREAM | PF_PBE) X(PF_STREAM | PF_TBE) X(PF_STREAM | PF_PBE | PF_TBE) \
@@ -396,46 +419,67 @@ struct PD3 : PairOps {
     static constexpr bool COLUMN = true;
     static constexpr int32_t FLOOR = 0x0400;
 
+    // PF_KLIT: K_j = j + (14 - j) G of band 15 for the form's |G_e|, both halves, as the signed 32-bit literal an "n" operand takes
+    template <int FORM> static constexpr int32_t klit(int j)     { return int32_t(uint32_t(j + (14 - j) * 32 * pair_ge(FORM)) * 0x10001u); }
+    template <int FORM> static constexpr int32_t pairlit()       { return int32_t(uint32_t(2 * 32 * pair_ge(FORM)) * 0x10001u); }
+
     // column 0 (no E): F' = max3(F'(i-1,1), S'(i-1,1), Z(i,0)), h = max(F', diagonal); its key seeds the row key, its S' is column 1's E'
+    // (the asm texts are macros: PF_DV, PF_KV and PF_KLIT run the same instructions with other operand classes)
+#define NVB_PD3_COL0 \
+            "v_perm_b32 %[d], %[thi], %[tlo], %[g0]\n\t" \
+            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
+            "v_add_u32 %[d], %[s0], %[d]\n\t" \
+            "v_pk_max_u16 %[h], %[f0], %[d]\n\t" \
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t" \
+            "v_add_u32 %[rk], %[k0], %[h]"
+#define NVB_PD3_COL0_OUT [f0] "=&v"(F0), [d] "=&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
+#define NVB_PD3_COL0_IN  [g0] "v"(g0), [tlo] "v"(tlo), [thi] "v"(thi), [f1] "v"(F1), [s1] "v"(S1), [z0] "s"(Z0)
+    template <int FORM>
     static __device__ __forceinline__ void col0(uint32_t& F0, const uint32_t F1, uint32_t& S0, const uint32_t S1, uint32_t& rowkey,
                                                 const uint32_t g0, const uint32_t D, const uint32_t tlo, const uint32_t thi, const uint32_t Z0, const uint32_t K0)
     {
         uint32_t d, h;
-        asm("v_perm_b32 %[d], %[thi], %[tlo], %[g0]\n\t"
-            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t"
-            "v_add_u32 %[d], %[s0], %[d]\n\t"
-            "v_pk_max_u16 %[h], %[f0], %[d]\n\t"
-            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
-            "v_add_u32 %[rk], %[k0], %[h]"
-            : [f0] "=&v"(F0), [d] "=&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
-            : [g0] "v"(g0), [tlo] "v"(tlo), [thi] "v"(thi), [f1] "v"(F1), [s1] "v"(S1), [dd] "s"(D), [z0] "s"(Z0), [k0] "s"(K0));
+        if constexpr ((FORM & PF_KLIT) != 0)    asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
+        else if constexpr ((FORM & PF_KV) != 0) asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "v"(K0));
+        else if constexpr ((FORM & PF_DV) != 0) asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "s"(K0));
+        else                                    asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "s"(D), [k0] "s"(K0));
     }
 
     // PM3::cell2 without E's subtracts: E'(J+1) = max(E'(J), S'(J)).  Ein: E'(i,J), read only (column 1's is S'(i,0), which stays live as
     // the next row's diagonal); E: E'(i,J+2).  Z0, Z1: Z(i,J), Z(i,J+1); K0, K1: K_J, K_(J+1); they and D are scalars, one to an instruction
+#define NVB_PD3_CELL2_T(P) \
+            "v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t" \
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t" \
+            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
+            "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z1]\n\t" \
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t" \
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t" P \
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t" \
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t" \
+            "v_add_u32 %[d0], %[k0], %[h]\n\t" P \
+            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t" \
+            "v_pk_maximum3_f16 %[h], %[f1], %[d1], %[e]\n\t" \
+            "v_subrev_u32 %[s1], %[dd], %[h]\n\t" \
+            "v_add_u32 %[d1], %[k1], %[h]\n\t" P \
+            "v_pk_max_u16 %[e], %[e], %[s1]\n\t" \
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+#define NVB_PD3_CELL2 NVB_PD3_CELL2_T("")
+#define NVB_PD3_CELL2_PAD NVB_PD3_CELL2_T("s_nop 0\n\t")
+#define NVB_PD3_CELL2_OUT [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
+#define NVB_PD3_CELL2_IN  [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1)
+    // J: the first of the two columns (PF_KLIT's literals are its and the next one's)
+    template <int FORM, int J>
     static __device__ __forceinline__ void cell2(uint32_t& F0, uint32_t& F1, const uint32_t F2, uint32_t& S0, uint32_t& S1, const uint32_t S2, const uint32_t Ein, uint32_t& E,
                                                  uint32_t& rowkey, const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
         uint32_t d0, d1, h;
-        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
-            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
-            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t"
-            "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z1]\n\t"
-            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
-            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
-            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
-            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
-            "v_add_u32 %[d0], %[k0], %[h]\n\t"
-            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
-            "v_pk_maximum3_f16 %[h], %[f1], %[d1], %[e]\n\t"
-            "v_subrev_u32 %[s1], %[dd], %[h]\n\t"
-            "v_add_u32 %[d1], %[k1], %[h]\n\t"
-            "v_pk_max_u16 %[e], %[e], %[s1]\n\t"
-            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
-            : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
-            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein),
-              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+        if constexpr ((FORM & PF_KLIT) != 0 && (FORM & PF_PAD) != 0) asm(NVB_PD3_CELL2_PAD : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_PAD) != 0) asm(NVB_PD3_CELL2_PAD : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
+        else if constexpr ((FORM & PF_KLIT) != 0) asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_KV) != 0) asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "v"(K0), [k1] "v"(K1));
+        else if constexpr ((FORM & PF_DV) != 0) asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "s"(K0), [k1] "s"(K1));
+        else                                    asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
     }
 
     // PF_ORDER (probe only): cell2's fifteen instructions in another order, one more temporary.  No instruction reads the result of the
@@ -468,27 +512,32 @@ struct PD3 : PairOps {
 
     // PM3::tail2 in the column frame: the cell J next to the band's edge (F' = max(S'(i-1,J+1), Z(i,J))) and the last column J + 1
     // (h = max3(E', diagonal, Z(i,J+1)))
+#define NVB_PD3_TAIL2 \
+            "v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t" \
+            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t" \
+            "v_pk_max_u16 %[f0], %[s1], %[z0]\n\t" \
+            "v_add_u32 %[d0], %[s0], %[d0]\n\t" \
+            "v_add_u32 %[d1], %[s1], %[d1]\n\t" \
+            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t" \
+            "v_subrev_u32 %[s0], %[dd], %[h]\n\t" \
+            "v_add_u32 %[d0], %[k0], %[h]\n\t" \
+            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t" \
+            "v_pk_maximum3_f16 %[h], %[e], %[d1], %[z1]\n\t" \
+            "v_subrev_u32 %[s1], %[dd], %[h]\n\t" \
+            "v_add_u32 %[d1], %[k1], %[h]\n\t" \
+            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+#define NVB_PD3_TAIL2_OUT [f0] "=&v"(F0), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
+#define NVB_PD3_TAIL2_IN  [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1)
+    template <int FORM, int J>
     static __device__ __forceinline__ void tail2(uint32_t& F0, uint32_t& S0, uint32_t& S1, const uint32_t Ein, uint32_t& rowkey,
                                                  const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
         uint32_t d0, d1, h, e;
-        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
-            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
-            "v_pk_max_u16 %[f0], %[s1], %[z0]\n\t"
-            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
-            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
-            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
-            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
-            "v_add_u32 %[d0], %[k0], %[h]\n\t"
-            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
-            "v_pk_maximum3_f16 %[h], %[e], %[d1], %[z1]\n\t"
-            "v_subrev_u32 %[s1], %[dd], %[h]\n\t"
-            "v_add_u32 %[d1], %[k1], %[h]\n\t"
-            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
-            : [f0] "=&v"(F0), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
-            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [ei] "v"(Ein),
-              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+        if constexpr ((FORM & PF_KLIT) != 0)    asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_KV) != 0) asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "v"(K0), [k1] "v"(K1));
+        else if constexpr ((FORM & PF_DV) != 0) asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "s"(K0), [k1] "s"(K1));
+        else                                    asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
     }
 
     // PF_ORDER (probe only): tail2's thirteen instructions in the order of cell2_ordered
@@ -524,8 +573,8 @@ struct PD3 : PairOps {
                 cell2_ordered(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
                               fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
             else
-                cell2(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
-                      fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
+                cell2<FORM, J>(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
+                               fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
             Cells<BAND, R, FORM, J + 2, END>::run(st, fr, En, E, rowkey, tlo, thi);
         }
     };
@@ -557,7 +606,7 @@ struct PD3 : PairOps {
         fr.z[(2 * R + BAND - 2) & 15] += fr.step;
         fr.z[(2 * R + BAND - 1) & 15] += fr.step;
         uint32_t rowkey, E;
-        col0(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, st.tc[R & 15], fr.D, tlo, thi, fr.z[(2 * R) & 15], fr.k[0]);
+        col0<FORM>(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, st.tc[R & 15], fr.D, tlo, thi, fr.z[(2 * R) & 15], fr.k[0]);
         // 1 <= j <= BAND-3, then BAND-2 and BAND-1
         Cells<BAND, R, FORM, 1, BAND - 2>::run(st, fr, st.S[0], E, rowkey, tlo, thi);
         st.tc[(R + BAND - 1) & 15] = g_new;
@@ -565,14 +614,14 @@ struct PD3 : PairOps {
             tail2_ordered(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
                           fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
         else
-            tail2(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
-                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+            tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
+                                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
         if constexpr ((FORM & PF_FOLD2) != 0)
         {
             // the header comment, "The pair fold": the even row's key moves into the odd row's frame (2 G up), the odd row's takes the
             // pair's bit, and one fold serves both under the even row's number
             if constexpr ((R & 1) == 0) rk2 = rowkey;
-            else fold<FORM>(st, mx(rk2 + fr.pair, rowkey + rep(16)) - fr.z[(2 * R + BAND - 1) & 15], i - 1u);
+            else fold<FORM>(st, mx(rk2 + ((FORM & PF_KLIT) ? uint32_t(pairlit<FORM>()) : fr.pair), rowkey + rep(16)) - fr.z[(2 * R + BAND - 1) & 15], i - 1u);
         }
         else fold<FORM>(st, rowkey - fr.z[(2 * R + BAND - 1) & 15], i);               // the row key stands in the last column's frame
     }
@@ -662,6 +711,8 @@ banded_gotoh_pair_kernel(const GotohParams p)
     static_assert(!(FORM & (PF_AHEAD | PF_FOLD2 | PF_ORDER)) || CELL::COLUMN, "the new row is the column frame's");
     static_assert(!AHEAD || !(FORM & PF_KO_TABLE), "no table reads, none ahead");
     static_assert(!FOLD2 || !(FORM & (PF_SINK_KEY | PF_KO_SINK | PF_KO_BOUND)), "the pair fold is the compare-and-select fold's, over the job's own rows");
+    static_assert(!(FORM & (PF_DV | PF_KV | PF_KLIT)) || (CELL::COLUMN && !(FORM & PF_ORDER)), "the constants' placements are the column frame's cell2 / tail2");
+    static_assert(!(FORM & PF_GE3) || (FORM & PF_KLIT), "|G_e| is the literal form's parameter");
     constexpr bool P4 = !(FORM & PF_PAT2), PBE = (FORM & PF_PBE) != 0, TBE = (FORM & PF_TBE) != 0;     // STREAM only: the host has matched them to the strings
     __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
     if (threadIdx.x < 16u)
@@ -695,6 +746,13 @@ banded_gotoh_pair_kernel(const GotohParams p)
     st.z = CELL::rep(d32 + g32 + CELL::FLOOR);                                     // BIAS
     ColumnFrame<BAND> fr;
     if constexpr (CELL::COLUMN) CELL::open(fr, d32, g32);                          // (st.z is not used then)
+    // the constants the form keeps in vector registers, resident like the row frame's D and G
+    if constexpr ((FORM & (PF_DV | PF_KV | PF_KLIT)) != 0) asm("" : "+v"(fr.D));
+    if constexpr ((FORM & PF_KV) != 0)
+    {
+        #pragma unroll
+        for (int j = 0; j < BAND; ++j) asm("" : "+v"(fr.k[j]));
+    }
     st.best[0] = st.best[1] = 0u; st.besti[0] = st.besti[1] = 0u;
     RowCarry carry = { { 0u, 0u, 0u, 0u }, 0u };
     {

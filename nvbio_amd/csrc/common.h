@@ -21,11 +21,14 @@ extern thread_local const char* g_last_pair_frame;
 // the row around its cells, "fold2" (PD3 by default: the sink folded once per two rows) or "plain":
 // nvbio_hip_last_kernel_row
 extern thread_local const char* g_last_pair_row;
+// where its cell keeps the key constants K_j, "literal" (PD3 with the pair fold by default, |G_e| <= 3) or "scalar":
+// nvbio_hip_last_kernel_const
+extern thread_local const char* g_last_pair_const;
 
 // Test switches (include/nvbio_hip.h, "Test switches"): alternative executions of the same results.  Each is an atomic int, seeded ONCE
 // from the environment variable of the same name (std::call_once) and changed afterwards only through nvbio_hip_set_test_switch --
 // no getenv on the launch paths, which run on several driver threads at a time.
-enum TestSwitch { SW_FORCE_32BIT = 0, SW_NO_STAGING, SW_FULL_GENERIC, SW_ED_SWEEP, SW_FULL_SINGLE_JOB, SW_FULL_ROWS, SW_TRACEBACK_LANES, SW_SELECT_LANES, SW_BANDED_PAIR, SW_PAIR_ROW, SW_COUNT };
+enum TestSwitch { SW_FORCE_32BIT = 0, SW_NO_STAGING, SW_FULL_GENERIC, SW_ED_SWEEP, SW_FULL_SINGLE_JOB, SW_FULL_ROWS, SW_TRACEBACK_LANES, SW_SELECT_LANES, SW_BANDED_PAIR, SW_PAIR_ROW, SW_PAIR_CONST, SW_COUNT };
 int test_switch(TestSwitch which);       // the switch's integer value; 0 = default execution
 
 // ---------------------------------------------------------------------------
