@@ -37,6 +37,7 @@
 //    Both produce the reference's int32 results bit for bit.
 //
 #include "banded_gotoh_bounded.h"
+#define NVB_PAIR_EXTERN                  // the pair kernel's instances are compiled elsewhere (banded_gotoh_pair.h)
 #include "banded_gotoh_pair.h"
 #include <mutex>
 #include <unordered_map>
@@ -49,12 +50,7 @@
 namespace nvb {
 
 thread_local const char* g_last_kernel = "";
-thread_local const char* g_last_pair = nullptr;
-thread_local const char* g_last_pair_cell = "";
-thread_local const char* g_last_pair_fetch = "";
-thread_local const char* g_last_pair_frame = "";
-thread_local const char* g_last_pair_row = "";
-thread_local const char* g_last_pair_const = "";
+thread_local PairLaunch g_last_pair;
 
 #define NVB_DECL(B) \
     extern template hipError_t launch_band_width<B, NoQual>(const GotohParams&, const NoQual&, int, bool, hipStream_t); \
@@ -68,19 +64,6 @@ NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
     extern template hipError_t launch_band_width_bounded<B, NoQual>(const GotohParams&, const NoQual&, const BoundArgs&, int, bool, hipStream_t); \
     extern template hipError_t launch_band_width_bounded<B, QualArgs>(const GotohParams&, const QualArgs&, const BoundArgs&, int, bool, hipStream_t);
 NVB_DECL(3) NVB_DECL(5) NVB_DECL(7) NVB_DECL(15) NVB_DECL(31)
-#undef NVB_DECL
-
-#define NVB_DECL(F) \
-    extern template hipError_t launch_band_pair<15, P16, (F)>(const GotohParams&, hipStream_t); \
-    extern template hipError_t launch_band_pair<15, PM3, (F)>(const GotohParams&, hipStream_t); \
-    extern template hipError_t launch_band_pair<15, PD3, (F)>(const GotohParams&, hipStream_t); \
-    extern template hipError_t launch_band_pair<15, PD3, (F) | PF_ROW2>(const GotohParams&, hipStream_t);
-NVB_DECL(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_DECL)
-#undef NVB_DECL
-#define NVB_DECL(F) extern template hipError_t launch_band_pair<15, PD3, (F)>(const GotohParams&, hipStream_t);
-#define NVB_DECL_GE(F) NVB_PAIR_GE_FORMS(NVB_DECL, F)
-NVB_DECL_GE(PF_SINK_VCC) NVB_PAIR_STREAM_FORMS(NVB_DECL_GE)
-#undef NVB_DECL_GE
 #undef NVB_DECL
 
 template <typename QA>
@@ -176,11 +159,11 @@ static bool pair_stream_admitted(const GotohParams& p)
 template <typename CELL, int ROW>
 static hipError_t launch_pair_row(const GotohParams& p, hipStream_t s)
 {
-    g_last_pair_row = (ROW & PF_ROW2) ? "fold2" : "plain";
-    g_last_pair_const = (ROW & PF_KLIT) ? "literal" : "scalar";
-    g_last_pair_fetch = "generic";
+    g_last_pair.row = (ROW & PF_ROW2) ? "fold2" : "plain";
+    g_last_pair.consts = (ROW & PF_CONST2) ? "literal" : "scalar";
+    g_last_pair.fetch = "generic";
     if (!pair_stream_admitted(p)) return launch_band_pair<15, CELL, PF_SINK_VCC | ROW>(p, s);
-    g_last_pair_fetch = "stream";
+    g_last_pair.fetch = "stream";
     switch (PF_STREAM | (p.pat.s.bits == 2u ? PF_PAT2 : 0) | (p.pat.s.big_endian ? PF_PBE : 0) | (p.txt.s.big_endian ? PF_TBE : 0)) {
 #define NVB_CASE(F) case (F): return launch_band_pair<15, CELL, (F) | ROW>(p, s);
     NVB_PAIR_STREAM_FORMS(NVB_CASE)
@@ -246,12 +229,7 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
                                  const nvb::BoundArgs* bound = nullptr, const bool asym = false, const bool plain_entry = false)
 {
     using namespace nvb;
-    g_last_pair = nullptr;
-    g_last_pair_cell = "";
-    g_last_pair_fetch = "";
-    g_last_pair_frame = "";
-    g_last_pair_row = "";
-    g_last_pair_const = "";
+    g_last_pair = PairLaunch();
     // NVBIO_HIP_FORCE_32BIT=1 disables the 16-bit kernels (used by the tests to cover both widths)
     // the row-frame kernels' limit (the plain launch); the limit of the recurrence as written (asymmetric costs, the bounded form -- and LOCAL jobs
     // between the two limits, which the plain launch hands to the A16P instance)
@@ -290,11 +268,11 @@ static int banded_gotoh_dispatch(nvb::GotohParams& p, const QA& qa, int64_t max_
     };
     p.plain16 = 0u;
     if (plain_entry && pair_admitted(p, type, band_len, lim16)) {
-        g_last_kernel = g_last_pair = tag16;
+        g_last_kernel = g_last_pair.kernel = tag16;
         const bool max3 = pair_max3_admitted(p);
         const bool column = max3 && pair_column_admitted(p);
-        g_last_pair_cell = max3 ? "max3" : "u16";
-        g_last_pair_frame = column ? "column" : "row";
+        g_last_pair.cell = max3 ? "max3" : "u16";
+        g_last_pair.frame = column ? "column" : "row";
         return column ? launch_pair<PD3>(p, s) : max3 ? launch_pair<PM3>(p, s) : launch_pair<P16>(p, s);
     }
     if (lim16 > 0 && (!fixed || patterns->fixed_length <= lim16)) {
@@ -778,9 +756,11 @@ NVB_API int nvbio_hip_host_free(void* ptr) { return ptr ? hipHostFree(ptr) : hip
 NVB_API int         nvbio_hip_abi_version(void) { return NVBIO_HIP_ABI_VERSION; }
 NVB_API const char* nvbio_hip_arch(void)        { return "gfx950"; }
 NVB_API const char* nvbio_hip_last_kernel(void) { return nvb::g_last_kernel; }
-NVB_API const char* nvbio_hip_last_kernel_detail(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? "pair" : ""; }
-NVB_API const char* nvbio_hip_last_kernel_fetch(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_fetch : ""; }
-NVB_API const char* nvbio_hip_last_kernel_frame(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_frame : ""; }
-NVB_API const char* nvbio_hip_last_kernel_row(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_row : ""; }
-NVB_API const char* nvbio_hip_last_kernel_const(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_const : ""; }
-NVB_API const char* nvbio_hip_last_kernel_cell(void) { return (nvb::g_last_pair && nvb::g_last_pair == nvb::g_last_kernel) ? nvb::g_last_pair_cell : ""; }
+// what the pair form's launch says of itself holds only while it is the last banded launch
+static const char* pair_fact(const char* fact) { return (nvb::g_last_pair.kernel && nvb::g_last_pair.kernel == nvb::g_last_kernel) ? fact : ""; }
+NVB_API const char* nvbio_hip_last_kernel_detail(void) { return pair_fact("pair"); }
+NVB_API const char* nvbio_hip_last_kernel_fetch(void)  { return pair_fact(nvb::g_last_pair.fetch); }
+NVB_API const char* nvbio_hip_last_kernel_frame(void)  { return pair_fact(nvb::g_last_pair.frame); }
+NVB_API const char* nvbio_hip_last_kernel_row(void)    { return pair_fact(nvb::g_last_pair.row); }
+NVB_API const char* nvbio_hip_last_kernel_const(void)  { return pair_fact(nvb::g_last_pair.consts); }
+NVB_API const char* nvbio_hip_last_kernel_cell(void)   { return pair_fact(nvb::g_last_pair.cell); }

@@ -100,21 +100,17 @@
 //     its pair's even row (q = rk(M-1) - Z(M-1,14), bit 4 clear), with Z(M-1,14) = BIAS' + G (2 M + 14) worked out once per job.
 //   tests/test_pair_fold2.py holds the arithmetic in numpy.
 //
-// Where the constants live.  D, the K_j and 2 G are wave-uniform; the column frame keeps them in scalar registers.  A v_add_u32 or
-// v_subrev_u32 with a scalar source issues at the rate of the packed ops, about 4.3 cycles, where the same op on vector registers or a
-// literal takes 2.3 (tools/valu_probe.hip, `mix`; profiles/banded_pair/README.md has the figures).  The forms compute the same values
-// from the same operations; only the operand's class changes, so pair_column_admitted and the numpy models do not:
-//   * PF_DV: D in one vector register, pinned as PM3 pins it.  PF_KV: the fifteen K_j in vector registers as well (four waves).
-//   * PF_KLIT: D in a vector register, K_j = j + (14 - j) G and 2 G as 32-bit literals: G = 32 |G_e| is then a template parameter, the
-//     PF_GE bits.  The column frame's byte admits |G_e| <= 3 for every scheme with max(match, mismatch) >= 0.
-//   * PF_PAD: one s_nop behind each of cell2's three groups of simple ops.  Alone none of the three placements gains more than 0.5 %:
-//     a simple op reaches its short issue only where a scalar instruction follows the group.  PF_KLIT | PF_PAD (PF_CONST2) is 5 % faster
-//     than the scalars and is what the library launches with the pair fold; NVBIO_HIP_PAIR_CONST = 1 keeps the scalars.
-//
-// Two forms that did not pay, kept for tools/pair_row_probe.hip alone (profiles/banded_pair/README.md has the figures).  PF_AHEAD
-// issues row R + 1's two table reads at the head of row R, hidden from the compiler in asm (it sinks a load it sees to its use), and
-// waits for them at the head of row R + 1: the same instructions, no exposed LDS round trip -- and no faster, the other four waves
-// of the SIMD were covering it.  PF_ORDER is cell2 / tail2 with the chain links E' -> h -> S' apart from each other: no faster either.
+// Where the constants live.  D, the K_j and 2 G are wave-uniform, and the column frame's cell has two placements for them; both compute
+// the same values from the same operations, so pair_column_admitted and the numpy models hold for either:
+//   * scalar registers, as "The column frame" has them;
+//   * PF_CONST2: D in a vector register, K_j = j + (14 - j) G and 2 G as 32-bit literals -- G = 32 |G_e| is then a template parameter,
+//     the PF_GE bits; the column frame's byte admits |G_e| <= 3 for every scheme with max(match, mismatch) >= 0 -- and one s_nop behind
+//     each of cell2's three groups of simple ops.
+// A v_add_u32 or v_subrev_u32 with a scalar source issues at the rate of the packed ops, about 4.3 cycles, where the same op on vector
+// registers or a literal takes 2.3 (tools/valu_probe.hip, `mix`), and it reaches that short issue only where a scalar instruction
+// follows the group: hence the pad.  Literals plus pad are 5 % faster than the scalars and are what the library launches with the pair
+// fold; NVBIO_HIP_PAIR_CONST = 1 keeps the scalars.  profiles/banded_pair/README.md has the figures, and those of the alternatives that
+// were measured and are gone: other placements of the constants, the table words read a row ahead, the cells' chain links spread apart.
 #pragma once
 #include "banded_gotoh_impl.h"
 
@@ -138,29 +134,34 @@ enum PairForm : int {
     PF_PAT2     = 2,                                                                //   the pattern has 2 bits (else 4)
     PF_PBE      = 8, PF_TBE = 256,                                                  //   the pattern's / the text's words are big-endian
     PF_KO_SINK  = 16, PF_KO_TABLE = 32, PF_KO_FETCH = 64, PF_KO_BOUND = 128,        // probe only
-    // the column frame's row (the header comment, "The pair fold" and "Two forms that did not pay"):
+    // the column frame's row (the header comment, "The pair fold"):
     PF_FOLD2    = 1024,                                                             //   the sink folds a pair of rows at a time
-    PF_AHEAD    = 512,                                                              //   a row's table words are read while the row before runs (probe only)
-    PF_ORDER    = 2048,                                                             //   the cells' chain links interleaved with their independent work (probe only)
-    // where the column frame's cell keeps its wave-uniform constants (the header comment, "Where the constants live"):
-    PF_DV       = 4096,                                                             //   D in a vector register
-    PF_KV       = 8192,                                                             //   D and the fifteen K_j in vector registers (probe only)
-    PF_KLIT     = 16384,                                                            //   D in a vector register, K_j and 2 G as literals: |G_e| is PF_GE's
-    PF_GE1      = 32768, PF_GE2 = 65536, PF_GE3 = PF_GE1 | PF_GE2,                  //   PF_KLIT's |G_e|, 0 ... 3 (pair_ge)
-    PF_PAD      = 131072                                                            //   an s_nop behind each group of simple ops in cell2 (scalars or PF_KLIT)
+    // the column frame's constants as literals with the pad (the header comment, "Where the constants live"); else scalar registers.
+    // Two bits, which were the literals and the pad apart: the forms keep their numbers and the kernels their names.  (512, 2048,
+    // 4096 and 8192 were forms that are gone and stay unused.)
+    PF_CONST2   = 16384 | 131072,
+    PF_GE1      = 32768, PF_GE2 = 65536, PF_GE3 = PF_GE1 | PF_GE2                   //   PF_CONST2's |G_e|, 0 ... 3 (pair_ge)
 };
 constexpr int pair_ge(int form)     { return (form / PF_GE1) & 3; }
 constexpr int pair_ge_bits(int ge)  { return ge * PF_GE1; }
-// the row the library launches for PD3 (banded_gotoh.hip: launch_pair; NVBIO_HIP_PAIR_ROW = 1 keeps the row without it)
+// the row the library launches for PD3 (banded_gotoh.hip: launch_pair; NVBIO_HIP_PAIR_ROW = 1 keeps the row without it).  With it the
+// library launches PF_CONST2 (NVBIO_HIP_PAIR_CONST = 1 keeps the scalars), one instance per |G_e| 0 ... 3 (a scheme with a larger
+// |G_e|, which only negative match scores admit, keeps the scalars too)
 constexpr int PF_ROW2 = PF_FOLD2;
-// the constants' placement the library launches for PD3 with PF_ROW2 (NVBIO_HIP_PAIR_CONST = 1 keeps the scalars): literals, one instance
-// per |G_e| 0 ... 3 (a scheme with a larger |G_e|, which only negative match scores admit, keeps the scalars too)
-constexpr int PF_CONST2 = PF_KLIT | PF_PAD;
-#define NVB_PAIR_GE_FORMS(X, F) X((F) | PF_ROW2 | PF_CONST2) X((F) | PF_ROW2 | PF_CONST2 | PF_GE1) X((F) | PF_ROW2 | PF_CONST2 | PF_GE2) X((F) | PF_ROW2 | PF_CONST2 | PF_GE3)
-// the streamed forms the library holds: every pattern width and byte order it streams
-#define NVB_PAIR_STREAM_FORMS(X) \
-    X(PF_STREAM) X(PF_STREAM | PF_PBE) X(PF_STREAM | PF_TBE) X(PF_STREAM | PF_PBE | PF_TBE) \
-    X(PF_STREAM | PF_PAT2) X(PF_STREAM | PF_PAT2 | PF_PBE) X(PF_STREAM | PF_PAT2 | PF_TBE) X(PF_STREAM | PF_PAT2 | PF_PBE | PF_TBE)
+// the streamed forms the library holds: every pattern width and byte order it streams.  X(form), or Y(A, form) with one more argument
+#define NVB_PAIR_STREAM_FORMS_(Y, A) \
+    Y(A, PF_STREAM) Y(A, PF_STREAM | PF_PBE) Y(A, PF_STREAM | PF_TBE) Y(A, PF_STREAM | PF_PBE | PF_TBE) \
+    Y(A, PF_STREAM | PF_PAT2) Y(A, PF_STREAM | PF_PAT2 | PF_PBE) Y(A, PF_STREAM | PF_PAT2 | PF_TBE) Y(A, PF_STREAM | PF_PAT2 | PF_PBE | PF_TBE)
+#define NVB_PAIR_APPLY_(X, F) X(F)
+#define NVB_PAIR_STREAM_FORMS(X) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_APPLY_, X)
+// every instance the library holds, as X(cell, form): the generic fetches and every streamed form, each for the three cells and PD3
+// with PF_ROW2, and for PD3 with PF_ROW2 | PF_CONST2 and each |G_e|.  In two parts, named for the two translation units that share
+// their compile time (banded_gotoh_pair_b15.hip, banded_gotoh_pair_b15_lit.hip)
+#define NVB_PAIR_CELLS_(X, F) X(P16, (F)) X(PM3, (F)) X(PD3, (F)) X(PD3, (F) | PF_ROW2)
+#define NVB_PAIR_GES_(X, F)   X(PD3, (F) | PF_ROW2 | PF_CONST2) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE1) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE2) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE3)
+#define NVB_PAIR_INSTANCES_B15(X)     NVB_PAIR_CELLS_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_CELLS_, X)
+#define NVB_PAIR_INSTANCES_B15_LIT(X) NVB_PAIR_GES_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_GES_, X)
+#define NVB_PAIR_INSTANCES(X)         NVB_PAIR_INSTANCES_B15(X) NVB_PAIR_INSTANCES_B15_LIT(X)
 
 // what both cells share: the replicated constants, the substitution lookup and the sink
 struct PairOps {
@@ -170,25 +171,6 @@ struct PairOps {
     // both jobs' text symbols of one band column as one byte selector: {g_A, zero, 4 + g_B, zero} picks entry g_A of tlo and g_B of thi
     static constexpr uint32_t SEL_BASE = 0x0C040C00u;
     static __device__ __forceinline__ uint32_t subst(uint32_t tlo, uint32_t thi, uint32_t sel) { return __builtin_amdgcn_perm(thi, tlo, sel); }
-
-    // PF_AHEAD (probe only): a table word read that the compiler does not see, so that it cannot sink it to its use: issued a row ahead, waited for
-    // by table_wait before the first cell reads it.  Every table_ahead is followed on every path by a table_wait naming its destination
-    // (PairRows::run, and the block loop's wait behind the rows).  addr: the LDS byte address.  before: a register the row's first cell
-    // reads, passed through untouched -- the cells' asm blocks are not volatile, and without it the compiler puts them ahead of the read
-    // and issues it a few instructions before the next row's wait
-    static __device__ __forceinline__ void table_ahead(uint32_t& t, const uint32_t addr, uint32_t& before)
-    {
-        asm volatile("ds_read_b32 %0, %2" : "=v"(t), "+v"(before) : "v"(addr));
-    }
-    static __device__ __forceinline__ void table_wait(uint32_t& tlo, uint32_t& thi)      { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tlo), "+v"(thi)); }
-    static __device__ __forceinline__ void table_wait(uint32_t (&t)[4])
-    {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-    }
-    static __device__ __forceinline__ uint32_t lds_address(const uint32_t* shared)
-    {
-        return uint32_t(uintptr_t((const __attribute__((address_space(3))) uint32_t*)shared));
-    }
 
     // the sink (dp_row: a later cell with an equal score wins); the row's keys lose its zero here.  The fold, the probe's key form of it
     // (the header comment, "The sink") and the probe's knock-out, which keeps the row key live through one packed maximum
@@ -419,12 +401,12 @@ struct PD3 : PairOps {
     static constexpr bool COLUMN = true;
     static constexpr int32_t FLOOR = 0x0400;
 
-    // PF_KLIT: K_j = j + (14 - j) G of band 15 for the form's |G_e|, both halves, as the signed 32-bit literal an "n" operand takes
+    // PF_CONST2: K_j = j + (14 - j) G of band 15 for the form's |G_e|, both halves, as the signed 32-bit literal an "n" operand takes
     template <int FORM> static constexpr int32_t klit(int j)     { return int32_t(uint32_t(j + (14 - j) * 32 * pair_ge(FORM)) * 0x10001u); }
     template <int FORM> static constexpr int32_t pairlit()       { return int32_t(uint32_t(2 * 32 * pair_ge(FORM)) * 0x10001u); }
 
     // column 0 (no E): F' = max3(F'(i-1,1), S'(i-1,1), Z(i,0)), h = max(F', diagonal); its key seeds the row key, its S' is column 1's E'
-    // (the asm texts are macros: PF_DV, PF_KV and PF_KLIT run the same instructions with other operand classes)
+    // (the asm texts are macros: PF_CONST2 runs the same instructions with other operand classes)
 #define NVB_PD3_COL0 \
             "v_perm_b32 %[d], %[thi], %[tlo], %[g0]\n\t" \
             "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
@@ -439,15 +421,14 @@ struct PD3 : PairOps {
                                                 const uint32_t g0, const uint32_t D, const uint32_t tlo, const uint32_t thi, const uint32_t Z0, const uint32_t K0)
     {
         uint32_t d, h;
-        if constexpr ((FORM & PF_KLIT) != 0)    asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
-        else if constexpr ((FORM & PF_KV) != 0) asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "v"(K0));
-        else if constexpr ((FORM & PF_DV) != 0) asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "s"(K0));
-        else                                    asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "s"(D), [k0] "s"(K0));
+        if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
+        else                                   asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "s"(D), [k0] "s"(K0));
     }
 
     // PM3::cell2 without E's subtracts: E'(J+1) = max(E'(J), S'(J)).  Ein: E'(i,J), read only (column 1's is S'(i,0), which stays live as
-    // the next row's diagonal); E: E'(i,J+2).  Z0, Z1: Z(i,J), Z(i,J+1); K0, K1: K_J, K_(J+1); they and D are scalars, one to an instruction
-#define NVB_PD3_CELL2_T(P) \
+    // the next row's diagonal); E: E'(i,J+2).  Z0, Z1: Z(i,J), Z(i,J+1); K0, K1: K_J, K_(J+1); they and D are scalars, one to an instruction.
+    // P: PF_CONST2's pad behind each group of simple ops, or nothing
+#define NVB_PD3_CELL2(P) \
             "v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t" \
             "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t" \
             "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
@@ -463,51 +444,17 @@ struct PD3 : PairOps {
             "v_add_u32 %[d1], %[k1], %[h]\n\t" P \
             "v_pk_max_u16 %[e], %[e], %[s1]\n\t" \
             "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
-#define NVB_PD3_CELL2 NVB_PD3_CELL2_T("")
-#define NVB_PD3_CELL2_PAD NVB_PD3_CELL2_T("s_nop 0\n\t")
 #define NVB_PD3_CELL2_OUT [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
 #define NVB_PD3_CELL2_IN  [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1)
-    // J: the first of the two columns (PF_KLIT's literals are its and the next one's)
+    // J: the first of the two columns (PF_CONST2's literals are its and the next one's)
     template <int FORM, int J>
     static __device__ __forceinline__ void cell2(uint32_t& F0, uint32_t& F1, const uint32_t F2, uint32_t& S0, uint32_t& S1, const uint32_t S2, const uint32_t Ein, uint32_t& E,
                                                  uint32_t& rowkey, const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
         uint32_t d0, d1, h;
-        if constexpr ((FORM & PF_KLIT) != 0 && (FORM & PF_PAD) != 0) asm(NVB_PD3_CELL2_PAD : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
-        else if constexpr ((FORM & PF_PAD) != 0) asm(NVB_PD3_CELL2_PAD : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
-        else if constexpr ((FORM & PF_KLIT) != 0) asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
-        else if constexpr ((FORM & PF_KV) != 0) asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "v"(K0), [k1] "v"(K1));
-        else if constexpr ((FORM & PF_DV) != 0) asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "s"(K0), [k1] "s"(K1));
-        else                                    asm(NVB_PD3_CELL2 : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
-    }
-
-    // PF_ORDER (probe only): cell2's fifteen instructions in another order, one more temporary.  No instruction reads the result of the
-    // one before it where independent work is left to put between them: the second v_perm, the second F', cell J + 1's diagonal add and
-    // cell J's key add stand between the links of E' -> h -> S'
-    static __device__ __forceinline__ void cell2_ordered(uint32_t& F0, uint32_t& F1, const uint32_t F2, uint32_t& S0, uint32_t& S1, const uint32_t S2, const uint32_t Ein, uint32_t& E,
-                                                         uint32_t& rowkey, const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
-                                                         const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
-    {
-        uint32_t d0, d1, h, h1;
-        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
-            "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t"
-            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
-            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
-            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
-            "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z1]\n\t"
-            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
-            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
-            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
-            "v_add_u32 %[d0], %[k0], %[h]\n\t"
-            "v_pk_maximum3_f16 %[h1], %[f1], %[d1], %[e]\n\t"
-            "v_subrev_u32 %[s1], %[dd], %[h1]\n\t"
-            "v_add_u32 %[d1], %[k1], %[h1]\n\t"
-            "v_pk_max_u16 %[e], %[e], %[s1]\n\t"
-            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
-            : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [h1] "=&v"(h1), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
-            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein),
-              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+        if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_CELL2("s_nop 0\n\t") : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else                                   asm(NVB_PD3_CELL2("") : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
     }
 
     // PM3::tail2 in the column frame: the cell J next to the band's edge (F' = max(S'(i-1,J+1), Z(i,J))) and the last column J + 1
@@ -534,34 +481,8 @@ struct PD3 : PairOps {
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
         uint32_t d0, d1, h, e;
-        if constexpr ((FORM & PF_KLIT) != 0)    asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
-        else if constexpr ((FORM & PF_KV) != 0) asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "v"(K0), [k1] "v"(K1));
-        else if constexpr ((FORM & PF_DV) != 0) asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "s"(K0), [k1] "s"(K1));
-        else                                    asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
-    }
-
-    // PF_ORDER (probe only): tail2's thirteen instructions in the order of cell2_ordered
-    static __device__ __forceinline__ void tail2_ordered(uint32_t& F0, uint32_t& S0, uint32_t& S1, const uint32_t Ein, uint32_t& rowkey,
-                                                         const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
-                                                         const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
-    {
-        uint32_t d0, d1, h, h1, e;
-        asm("v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t"
-            "v_pk_max_u16 %[f0], %[s1], %[z0]\n\t"
-            "v_add_u32 %[d0], %[s0], %[d0]\n\t"
-            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
-            "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t"
-            "v_add_u32 %[d1], %[s1], %[d1]\n\t"
-            "v_subrev_u32 %[s0], %[dd], %[h]\n\t"
-            "v_add_u32 %[d0], %[k0], %[h]\n\t"
-            "v_pk_max_u16 %[e], %[ei], %[s0]\n\t"
-            "v_pk_maximum3_f16 %[h1], %[e], %[d1], %[z1]\n\t"
-            "v_subrev_u32 %[s1], %[dd], %[h1]\n\t"
-            "v_add_u32 %[d1], %[k1], %[h1]\n\t"
-            "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
-            : [f0] "=&v"(F0), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [h1] "=&v"(h1), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
-            : [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [ei] "v"(Ein),
-              [dd] "s"(D), [z0] "s"(Z0), [z1] "s"(Z1), [k0] "s"(K0), [k1] "s"(K1));
+        if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else                                   asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
     }
 
     template <int BAND, int R, int FORM, int J, int END>
@@ -569,12 +490,8 @@ struct PD3 : PairOps {
         static __device__ __forceinline__ void run(PairState<BAND>& st, const ColumnFrame<BAND>& fr, const uint32_t Ein, uint32_t& E, uint32_t& rowkey, const uint32_t tlo, const uint32_t thi)
         {
             uint32_t En;
-            if constexpr ((FORM & PF_ORDER) != 0)
-                cell2_ordered(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
-                              fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
-            else
-                cell2<FORM, J>(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
-                               fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
+            cell2<FORM, J>(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, st.tc[(R + J) & 15], st.tc[(R + J + 1) & 15], fr.D, tlo, thi,
+                           fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
             Cells<BAND, R, FORM, J + 2, END>::run(st, fr, En, E, rowkey, tlo, thi);
         }
     };
@@ -610,18 +527,14 @@ struct PD3 : PairOps {
         // 1 <= j <= BAND-3, then BAND-2 and BAND-1
         Cells<BAND, R, FORM, 1, BAND - 2>::run(st, fr, st.S[0], E, rowkey, tlo, thi);
         st.tc[(R + BAND - 1) & 15] = g_new;
-        if constexpr ((FORM & PF_ORDER) != 0)
-            tail2_ordered(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
-                          fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
-        else
-            tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
-                                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
+                              fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
         if constexpr ((FORM & PF_FOLD2) != 0)
         {
             // the header comment, "The pair fold": the even row's key moves into the odd row's frame (2 G up), the odd row's takes the
             // pair's bit, and one fold serves both under the even row's number
             if constexpr ((R & 1) == 0) rk2 = rowkey;
-            else fold<FORM>(st, mx(rk2 + ((FORM & PF_KLIT) ? uint32_t(pairlit<FORM>()) : fr.pair), rowkey + rep(16)) - fr.z[(2 * R + BAND - 1) & 15], i - 1u);
+            else fold<FORM>(st, mx(rk2 + ((FORM & PF_CONST2) ? uint32_t(pairlit<FORM>()) : fr.pair), rowkey + rep(16)) - fr.z[(2 * R + BAND - 1) & 15], i - 1u);
         }
         else fold<FORM>(st, rowkey - fr.z[(2 * R + BAND - 1) & 15], i);               // the row key stands in the last column's frame
     }
@@ -635,51 +548,22 @@ struct PD3 : PairOps {
     }
 };
 
-// what the column frame's row carries from one row to the next (PF_AHEAD, PF_FOLD2; unused otherwise)
-struct RowCarry {
-    uint32_t t[4];           // the table words of the even rows, {t[0], t[1]}, and of the odd rows, {t[2], t[3]}: one pair in use, one on its way
-    uint32_t rk2;            // the even row's row key
-};
-
 template <typename CELL, int BAND, int FORM, int R, int END>
 struct PairRows {
     // XT[0] / XT[1]: the block's entering text symbols 0-7 / 8-15, job A's in the low half and job B's in the high half
     // (KT: the resident table of the probe's PF_KO_TABLE, otherwise unused)
     // fr: the column frame's scalars (CELL::COLUMN; the row-frame cells take D and G instead)
-    // PF_AHEAD (probe only): row R waits for its own two table words, issues row R + 1's (rows 1 ... 15; the pattern's nibbles of all sixteen rows are
-    // in PA / PB, and a nibble past the pattern's end still indexes the table's sixteen entries) and then runs its cells.  Row 0 issues
-    // its own first: one exposed wait per block.  The read-ahead does not ask whether row R + 1 will run; the kernel waits once more
-    // behind the block's rows, so that no read is in flight when its register changes hands.
+    // rk2: the even row's row key, which the column frame's row carries to the odd row (PF_FOLD2; unused otherwise)
     static __device__ __forceinline__ void run(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
-                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab, const uint32_t (&KT)[2], RowCarry& c)
+                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab, const uint32_t (&KT)[2], uint32_t& rk2)
     {
         if ((FORM & PF_KO_BOUND) || i0 + R < M)
         {
             const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
             if constexpr (CELL::COLUMN)
             {
-                if constexpr ((FORM & PF_AHEAD) != 0)
-                {
-                    constexpr int C = 2 * (R & 1), N = 2 - C;                      // this row's pair of c.t and the next row's
-                    const uint32_t base = CELL::lds_address(tab);
-                    if (R == 0)
-                    {
-                        CELL::table_ahead(c.t[0], base + 4u * (uint32_t(PA) & 15u), st.S[0]);
-                        CELL::table_ahead(c.t[1], base + 4u * (uint32_t(PB) & 15u), st.S[0]);
-                    }
-                    CELL::table_wait(c.t[C], c.t[C + 1]);
-                    if (R + 1 < 16)
-                    {
-                        CELL::table_ahead(c.t[N], base + 4u * (uint32_t(PA >> (4 * ((R + 1) & 15))) & 15u), st.S[0]);
-                        CELL::table_ahead(c.t[N + 1], base + 4u * (uint32_t(PB >> (4 * ((R + 1) & 15))) & 15u), st.S[0]);
-                    }
-                    CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, c.t[C], c.t[C + 1], c.rk2);
-                    // the rows behind one that does not run do not run either: they are asked from inside this one, so that no path
-                    // leads from a read-ahead into a later row past the wait of the row between them
-                    PairRows<CELL, BAND, FORM, R + 1, END>::run(st, fr, i0, M, D, G, PA, PB, XT, tab, KT, c);
-                }
-                else if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, KT[0], KT[1], c.rk2);
-                else                         CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u], c.rk2);
+                if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, KT[0], KT[1], rk2);
+                else                    CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u], rk2);
             }
             else
             {
@@ -687,11 +571,11 @@ struct PairRows {
                 else                    CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
             }
         }
-        if constexpr (!(FORM & PF_AHEAD)) PairRows<CELL, BAND, FORM, R + 1, END>::run(st, fr, i0, M, D, G, PA, PB, XT, tab, KT, c);
+        PairRows<CELL, BAND, FORM, R + 1, END>::run(st, fr, i0, M, D, G, PA, PB, XT, tab, KT, rk2);
     }
 };
 template <typename CELL, int BAND, int FORM, int END> struct PairRows<CELL, BAND, FORM, END, END> {
-    static __device__ __forceinline__ void run(PairState<BAND>&, ColumnFrame<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2], RowCarry&) {}
+    static __device__ __forceinline__ void run(PairState<BAND>&, ColumnFrame<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2], uint32_t&) {}
 };
 
 // Lane k of the launch takes jobs 2k and 2k + 1 (with an odd n the last lane computes its one job in both halves).  The host has
@@ -707,12 +591,10 @@ __global__ void __launch_bounds__(PAIR_LANES)
 banded_gotoh_pair_kernel(const GotohParams p)
 {
     static_assert(BAND >= 3 && BAND <= 16, "the ring of 16");
-    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0, AHEAD = (FORM & PF_AHEAD) != 0, FOLD2 = (FORM & PF_FOLD2) != 0;
-    static_assert(!(FORM & (PF_AHEAD | PF_FOLD2 | PF_ORDER)) || CELL::COLUMN, "the new row is the column frame's");
-    static_assert(!AHEAD || !(FORM & PF_KO_TABLE), "no table reads, none ahead");
+    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0, FOLD2 = (FORM & PF_FOLD2) != 0;
+    static_assert(!(FORM & (PF_FOLD2 | PF_CONST2)) || CELL::COLUMN, "the pair fold and the literals are the column frame's");
     static_assert(!FOLD2 || !(FORM & (PF_SINK_KEY | PF_KO_SINK | PF_KO_BOUND)), "the pair fold is the compare-and-select fold's, over the job's own rows");
-    static_assert(!(FORM & (PF_DV | PF_KV | PF_KLIT)) || (CELL::COLUMN && !(FORM & PF_ORDER)), "the constants' placements are the column frame's cell2 / tail2");
-    static_assert(!(FORM & PF_GE3) || (FORM & PF_KLIT), "|G_e| is the literal form's parameter");
+    static_assert(!(FORM & PF_GE3) || (FORM & PF_CONST2), "|G_e| is the literal form's parameter");
     constexpr bool P4 = !(FORM & PF_PAT2), PBE = (FORM & PF_PBE) != 0, TBE = (FORM & PF_TBE) != 0;     // STREAM only: the host has matched them to the strings
     __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
     if (threadIdx.x < 16u)
@@ -746,15 +628,9 @@ banded_gotoh_pair_kernel(const GotohParams p)
     st.z = CELL::rep(d32 + g32 + CELL::FLOOR);                                     // BIAS
     ColumnFrame<BAND> fr;
     if constexpr (CELL::COLUMN) CELL::open(fr, d32, g32);                          // (st.z is not used then)
-    // the constants the form keeps in vector registers, resident like the row frame's D and G
-    if constexpr ((FORM & (PF_DV | PF_KV | PF_KLIT)) != 0) asm("" : "+v"(fr.D));
-    if constexpr ((FORM & PF_KV) != 0)
-    {
-        #pragma unroll
-        for (int j = 0; j < BAND; ++j) asm("" : "+v"(fr.k[j]));
-    }
+    if constexpr ((FORM & PF_CONST2) != 0) asm("" : "+v"(fr.D));                   // PF_CONST2's D: a vector register, resident like the row frame's D and G
     st.best[0] = st.best[1] = 0u; st.besti[0] = st.besti[1] = 0u;
-    RowCarry carry = { { 0u, 0u, 0u, 0u }, 0u };
+    uint32_t rk2 = 0u;                                                             // PF_FOLD2: the even row's row key
     {
         const uint32_t TA = fetch16_2bit(ts[0], tb[0]), TB = fetch16_2bit(ts[1], tb[1]);
         #pragma unroll
@@ -799,8 +675,7 @@ banded_gotoh_pair_kernel(const GotohParams p)
             TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1); TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
         }
         const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
-        PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, PA, PB, XT, s_tab, KT, carry);
-        if constexpr (AHEAD) CELL::table_wait(carry.t);                            // the read-ahead of a row that did not run
+        PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, PA, PB, XT, s_tab, KT, rk2);
         if (FORM & PF_KO_FETCH)
         {
             PA = (PA << 4) | (PA >> 60); PB = (PB << 8) | (PB >> 56);
@@ -815,7 +690,7 @@ banded_gotoh_pair_kernel(const GotohParams p)
         else { PA = PAn; PB = PBn; TA = TAn; TB = TBn; }
     }
 
-    if constexpr (FOLD2) { if (M & 1u) CELL::template fold_last<BAND, FORM>(st, carry.rk2, M, d32, g32); }
+    if constexpr (FOLD2) { if (M & 1u) CELL::template fold_last<BAND, FORM>(st, rk2, M, d32, g32); }
     #pragma unroll
     for (int h = 0; h < 2; ++h)
     {
@@ -835,5 +710,13 @@ hipError_t launch_band_pair(const GotohParams& p, hipStream_t stream)
     hipLaunchKernelGGL((banded_gotoh_pair_kernel<BAND, CELL, FORM>), dim3((n_lanes + PAIR_LANES - 1u) / PAIR_LANES), dim3(PAIR_LANES), 0, stream, p);
     return hipGetLastError();
 }
+
+// The library's instances (NVB_PAIR_INSTANCES) are compiled in banded_gotoh_pair_b15.hip and banded_gotoh_pair_b15_lit.hip.  A translation unit that launches them and must not compile them again defines NVB_PAIR_EXTERN before
+// it includes this header: banded_gotoh.hip does; the two instantiation files, and tools/pair_row_probe.hip with its own forms, do not
+#ifdef NVB_PAIR_EXTERN
+#define NVB_DECL(CELL, F) extern template hipError_t launch_band_pair<15, CELL, (F)>(const GotohParams&, hipStream_t);
+NVB_PAIR_INSTANCES(NVB_DECL)
+#undef NVB_DECL
+#endif
 
 } // namespace nvb

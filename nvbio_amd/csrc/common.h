@@ -10,20 +10,17 @@ namespace nvb {
 
 // thread-local name of the last kernel variant launched (introspection for tests/bench)
 extern thread_local const char* g_last_kernel;
-// the g_last_kernel value of the last launch that took the two-jobs-per-lane form (banded_gotoh_pair.h), or NULL: nvbio_hip_last_kernel_detail
-extern thread_local const char* g_last_pair;
-// which cell that launch ran, "u16" or "max3": nvbio_hip_last_kernel_cell
-extern thread_local const char* g_last_pair_cell;
-// how its block loop read the strings, "stream" or "generic": nvbio_hip_last_kernel_fetch
-extern thread_local const char* g_last_pair_fetch;
-// the frame its cell holds, "column" (PD3) or "row" (PM3, P16): nvbio_hip_last_kernel_frame
-extern thread_local const char* g_last_pair_frame;
-// the row around its cells, "fold2" (PD3 by default: the sink folded once per two rows) or "plain":
-// nvbio_hip_last_kernel_row
-extern thread_local const char* g_last_pair_row;
-// where its cell keeps the key constants K_j, "literal" (PD3 with the pair fold by default, |G_e| <= 3) or "scalar":
-// nvbio_hip_last_kernel_const
-extern thread_local const char* g_last_pair_const;
+// the last banded launch, if it took the two-jobs-per-lane form (banded_gotoh_pair.h): what nvbio_hip_last_kernel_detail, _cell,
+// _fetch, _frame, _row and _const answer, which is "" unless `kernel` is still g_last_kernel
+struct PairLaunch {
+    const char* kernel = nullptr;   // the g_last_kernel value of that launch, or NULL
+    const char* cell   = "";        // the cell it ran, "u16" or "max3"
+    const char* fetch  = "";        // how its block loop read the strings, "stream" or "generic"
+    const char* frame  = "";        // the frame its cell holds, "column" (PD3) or "row" (PM3, P16)
+    const char* row    = "";        // the row around its cells, "fold2" (PD3 by default: the sink folded once per two rows) or "plain"
+    const char* consts = "";        // where its cell keeps the key constants K_j, "literal" (PD3 with the pair fold by default, |G_e| <= 3) or "scalar"
+};
+extern thread_local PairLaunch g_last_pair;
 
 // Test switches (include/nvbio_hip.h, "Test switches"): alternative executions of the same results.  Each is an atomic int, seeded ONCE
 // from the environment variable of the same name (std::call_once) and changed afterwards only through nvbio_hip_set_test_switch --
