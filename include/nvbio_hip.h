@@ -1129,7 +1129,7 @@ void nvbio_hip_comm_set_transport(const nvbio_hip_comm_transport* transport);
 
 /* Test switches.  A few named integers select alternative executions of the same results, for the parity suite to cover both
  * (NVBIO_HIP_FORCE_32BIT, NVBIO_HIP_NO_STAGING, NVBIO_HIP_FULL_GENERIC, NVBIO_HIP_FULL_SINGLE_JOB, NVBIO_HIP_FULL_ROWS, NVBIO_HIP_ED_SWEEP,
- * NVBIO_HIP_SELECT_LANES, NVBIO_HIP_TRACEBACK_LANES, NVBIO_HIP_BANDED_PAIR, NVBIO_HIP_PAIR_ROW, NVBIO_HIP_PAIR_CONST).  Each is seeded ONCE per process from the environment variable of the same name and
+ * NVBIO_HIP_SELECT_LANES, NVBIO_HIP_TRACEBACK_LANES, NVBIO_HIP_BANDED_PAIR, NVBIO_HIP_PAIR_ROW, NVBIO_HIP_PAIR_CONST, NVBIO_HIP_PAIR_SUB).  Each is seeded ONCE per process from the environment variable of the same name and
  * changed afterwards only through nvbio_hip_set_test_switch (atomic; safe while other threads are inside library calls -- a call in flight
  * uses the value it read when it started).  0 = the default execution.  Production code leaves them alone. */
 int nvbio_hip_set_test_switch(const char* name, int value);     /* hipErrorInvalidValue for an unknown name */
@@ -1162,6 +1162,7 @@ const char* nvbio_hip_last_kernel_cell(void);    /* the cell of a "pair" launch:
 const char* nvbio_hip_last_kernel_frame(void);   /* the frame of a "pair" launch's cell: "column" (no gap subtract on the horizontal step) or "row", else "" */
 const char* nvbio_hip_last_kernel_row(void);     /* the row of a "pair" launch around its cells: "fold2" (the sink folded once per two rows: the "column" frame unless NVBIO_HIP_PAIR_ROW is 1) or "plain", else "" */
 const char* nvbio_hip_last_kernel_const(void);   /* where a "pair" launch's cell keeps its key constants: "literal" (in the instructions: the "fold2" row unless NVBIO_HIP_PAIR_CONST is 1 or |gap_ext| > 3), "vector" (no launch of the library's) or "scalar", else "" */
+const char* nvbio_hip_last_kernel_sub(void);     /* where a "pair" launch's cell takes its substitution words from: "lds" (one LDS read per cell: the "literal" form unless NVBIO_HIP_PAIR_SUB is 1) or "perm" (a v_perm_b32 lookup in two table words per row), else "" */
 const char* nvbio_hip_last_kernel_fetch(void);   /* how a "pair" launch read its strings: "stream" (32-bit cursors, only new words loaded) or "generic", else "" */
 
 #ifdef __cplusplus

@@ -111,6 +111,30 @@
 // follows the group: hence the pad.  Literals plus pad are 5 % faster than the scalars and are what the library launches with the pair
 // fold; NVBIO_HIP_PAIR_CONST = 1 keeps the scalars.  profiles/banded_pair/README.md has the figures, and those of the alternatives that
 // were measured and are gone: other placements of the constants, the table words read a row ahead, the cells' chain links spread apart.
+//
+// Where the substitution comes from.  A diagonal adds one word to S'(i-1,j): job A's byte in bits 0-7, job B's in bits 16-23, each the
+// match byte where the pattern's nibble equals the text's symbol and the mismatch byte elsewhere (in the column frame both carry the
+// extra G).  Two ways to that word, the same bytes either way, so every bound above and pair_column_admitted hold for both:
+//   * the lookup: the row reads two table words from LDS, s_tab[nibble A] and s_tab[nibble B] (entry q: the match byte in byte q where
+//     q < 4, the mismatch byte in every other byte), and each column takes one v_perm_b32 of them with its selector {g_A, zero, 4 + g_B,
+//     zero}, which the ring tc[] holds.  Fifteen v_perm_b32 per row, a slow op on the vector ALU (4.3 cycles), and six instructions for
+//     the two words.  Every instance has it but the ones below.
+//   * PF_SUBLDS, which the library launches with PF_FOLD2 | PF_CONST2: the LDS pipe does the lookup.  With c = nibble ^ symbol, a job's
+//     byte is the match byte exactly where c == 0 (a nibble of 4 or more gives c >= 4 against every symbol: N and an 8-bit pattern's
+//     code 15 match nothing, as s_tab[q >= 4] has it).  A 256-word table s_sub, filled once per block, holds {0, sub(c_B), 0, sub(c_A)} at
+//     sub_index(c_A, c_B) = c_A & 3 | c_B << 2 | (c_A >> 2) << 6; the sixteen words two A/C/G/T codes reach are then words 0 ... 15, one
+//     to a bank, where the plain c_A | c_B << 4 would put c_B = 0 and c_B = 2 into the same banks.  xor goes bit by bit, so the index
+//     is the xor of a row word, both jobs' nibbles in that layout, and a column word, t_A | t_B << 2; both are kept times 4, as byte
+//     offsets, and a cell costs one v_xor_b32 on two vector registers (a simple op) and one ds_read_b32.
+//       - the row words: once per 16-row block, two shifts and two v_bfi_b32 per word put the block's rows into four words, a byte per
+//         row (sub_row_words); a row takes its byte with one SDWA shift.
+//       - the column words: the ring tc[] holds them in place of the selectors.  Once per block two v_bfi_b32 interleave the sixteen
+//         entering symbols of both jobs, a nibble per row; a row takes its nibble with a shift and a mask.
+//       - the reads: eight at the row's head, seven behind column 4 into the registers columns 0 ... 4 have given back (fifteen
+//         landing registers at once do not fit the 96 of five waves), each batch in the order the cells take its words.  They are plain
+//         loads; the compiler writes a counted s_waitcnt lgkmcnt before each cell block.
+//     The row has 1 + 2 + 15 simple ops where the lookup has 7 simple and 15 slow ones and two reads; it is 4 to 5 % faster
+//     (profiles/banded_pair/README.md).  NVBIO_HIP_PAIR_SUB = 1 keeps the lookup.
 #pragma once
 #include "banded_gotoh_impl.h"
 
@@ -120,7 +144,7 @@ template <int BAND>
 struct PairState {
     uint32_t S[BAND];        // S = H' + G_o - G_e of the previous row, both jobs
     uint32_t F[BAND - 1];
-    uint32_t tc[16];         // the band's text symbols, as selectors (a ring indexed by (row + column) & 15, like BandTraits)
+    uint32_t tc[16];         // the band's text symbols, as selectors or, under PF_SUBLDS, column words (a ring indexed by (row + column) & 15, like BandTraits)
     uint32_t z;              // the row's zero
     uint32_t best[2], besti[2];   // per job: the best key so far (score * 32 + j) and its row
 };
@@ -140,13 +164,18 @@ enum PairForm : int {
     // Two bits, which were the literals and the pad apart: the forms keep their numbers and the kernels their names.  (512, 2048,
     // 4096 and 8192 were forms that are gone and stay unused.)
     PF_CONST2   = 16384 | 131072,
-    PF_GE1      = 32768, PF_GE2 = 65536, PF_GE3 = PF_GE1 | PF_GE2                   //   PF_CONST2's |G_e|, 0 ... 3 (pair_ge)
+    PF_GE1      = 32768, PF_GE2 = 65536, PF_GE3 = PF_GE1 | PF_GE2,                  //   PF_CONST2's |G_e|, 0 ... 3 (pair_ge)
+    // the substitution words read from LDS, one ds_read_b32 per cell, in place of the v_perm_b32 lookup (the header comment, "Where the
+    // substitution comes from"); with PF_FOLD2 | PF_CONST2 only
+    PF_SUBLDS   = 262144,
+    PF_KO_PERM  = 524288                                                            // probe only: PF_CONST2's row, a v_xor_b32 for each v_perm_b32
 };
 constexpr int pair_ge(int form)     { return (form / PF_GE1) & 3; }
 constexpr int pair_ge_bits(int ge)  { return ge * PF_GE1; }
 // the row the library launches for PD3 (banded_gotoh.hip: launch_pair; NVBIO_HIP_PAIR_ROW = 1 keeps the row without it).  With it the
 // library launches PF_CONST2 (NVBIO_HIP_PAIR_CONST = 1 keeps the scalars), one instance per |G_e| 0 ... 3 (a scheme with a larger
-// |G_e|, which only negative match scores admit, keeps the scalars too)
+// |G_e|, which only negative match scores admit, keeps the scalars too), and with PF_CONST2 it launches PF_SUBLDS
+// (NVBIO_HIP_PAIR_SUB = 1 keeps the lookup)
 constexpr int PF_ROW2 = PF_FOLD2;
 // the streamed forms the library holds: every pattern width and byte order it streams.  X(form), or Y(A, form) with one more argument
 #define NVB_PAIR_STREAM_FORMS_(Y, A) \
@@ -155,13 +184,39 @@ constexpr int PF_ROW2 = PF_FOLD2;
 #define NVB_PAIR_APPLY_(X, F) X(F)
 #define NVB_PAIR_STREAM_FORMS(X) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_APPLY_, X)
 // every instance the library holds, as X(cell, form): the generic fetches and every streamed form, each for the three cells and PD3
-// with PF_ROW2, and for PD3 with PF_ROW2 | PF_CONST2 and each |G_e|.  In two parts, named for the two translation units that share
-// their compile time (banded_gotoh_pair_b15.hip, banded_gotoh_pair_b15_lit.hip)
+// with PF_ROW2, and for PD3 with PF_ROW2 | PF_CONST2 and each |G_e|, with the v_perm_b32 lookup and with PF_SUBLDS.  In three parts,
+// named for the three translation units that share their compile time (banded_gotoh_pair_b15.hip, banded_gotoh_pair_b15_lit.hip for
+// the lookup, banded_gotoh_pair_b15_sub.hip for PF_SUBLDS)
 #define NVB_PAIR_CELLS_(X, F) X(P16, (F)) X(PM3, (F)) X(PD3, (F)) X(PD3, (F) | PF_ROW2)
 #define NVB_PAIR_GES_(X, F)   X(PD3, (F) | PF_ROW2 | PF_CONST2) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE1) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE2) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE3)
 #define NVB_PAIR_INSTANCES_B15(X)     NVB_PAIR_CELLS_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_CELLS_, X)
 #define NVB_PAIR_INSTANCES_B15_LIT(X) NVB_PAIR_GES_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_GES_, X)
-#define NVB_PAIR_INSTANCES(X)         NVB_PAIR_INSTANCES_B15(X) NVB_PAIR_INSTANCES_B15_LIT(X)
+#define NVB_PAIR_SUBS_(X, F)  NVB_PAIR_GES_(X, (F) | PF_SUBLDS)
+#define NVB_PAIR_INSTANCES_B15_SUB(X) NVB_PAIR_SUBS_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_SUBS_, X)
+#define NVB_PAIR_INSTANCES(X)         NVB_PAIR_INSTANCES_B15(X) NVB_PAIR_INSTANCES_B15_LIT(X) NVB_PAIR_INSTANCES_B15_SUB(X)
+
+// PF_SUBLDS's table index (the header comment, "Where the substitution comes from"): with c = nibble ^ symbol of job A and of job B,
+//   index = c_A & 3 | c_B << 2 | (c_A >> 2) << 6,
+// so the sixteen entries two A/C/G/T codes reach are words 0 ... 15, one to a bank.  xor goes bit by bit, so the index is the xor of a
+// row word (both nibbles in that layout) and a column word (t_A | t_B << 2); both are kept as byte offsets, times 4.
+__host__ __device__ constexpr uint32_t sub_index(uint32_t ca, uint32_t cb) { return (ca & 3u) | (cb << 2) | ((ca >> 2) << 6); }
+__host__ __device__ constexpr uint32_t sub_code_a(uint32_t index)          { return (index & 3u) | ((index >> 6) << 2); }
+__host__ __device__ constexpr uint32_t sub_code_b(uint32_t index)          { return (index >> 2) & 15u; }
+__device__ __forceinline__ uint32_t sub_bfi(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); }     // v_bfi_b32
+// a 16-row block's row words, a byte each: byte k of RE is row 2 k's, byte k of RO row 2 k + 1's (PA, PB: the rows' nibbles, row r's at
+// bit 4 r).  Two shifts and two v_bfi_b32 per word: the nibble's low pair, the other job's nibble, the nibble's high pair.
+__device__ __forceinline__ void sub_row_words(const uint64_t PA, const uint64_t PB, uint64_t& RE, uint64_t& RO)
+{
+    uint32_t re[2], ro[2];
+    #pragma unroll
+    for (int h = 0; h < 2; ++h)
+    {
+        const uint32_t a = uint32_t(PA >> (32 * h)), b = uint32_t(PB >> (32 * h));
+        re[h] = sub_bfi(0x03030303u, a,      sub_bfi(0x3C3C3C3Cu, b << 2, a << 4));
+        ro[h] = sub_bfi(0x03030303u, a >> 4, sub_bfi(0x3C3C3C3Cu, b >> 2, a));
+    }
+    RE = re[0] | uint64_t(re[1]) << 32; RO = ro[0] | uint64_t(ro[1]) << 32;
+}
 
 // what both cells share: the replicated constants, the substitution lookup and the sink
 struct PairOps {
@@ -407,8 +462,14 @@ struct PD3 : PairOps {
 
     // column 0 (no E): F' = max3(F'(i-1,1), S'(i-1,1), Z(i,0)), h = max(F', diagonal); its key seeds the row key, its S' is column 1's E'
     // (the asm texts are macros: PF_CONST2 runs the same instructions with other operand classes)
-#define NVB_PD3_COL0 \
-            "v_perm_b32 %[d], %[thi], %[tlo], %[g0]\n\t" \
+    // L: where the diagonals' substitution words come from (the header comment, "Where the substitution comes from"): the lookup, one
+    // v_perm_b32 per column; nothing under PF_SUBLDS, whose words arrive from LDS in g0 / g1; the probe's PF_KO_PERM, a v_xor_b32 of two
+    // resident registers in the lookup's place
+#define NVB_PD3_PERM1 "v_perm_b32 %[d], %[thi], %[tlo], %[g0]\n\t"
+#define NVB_PD3_PERM2 "v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t" "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
+#define NVB_PD3_XOR1  "v_xor_b32 %[d], %[tlo], %[g0]\n\t"
+#define NVB_PD3_XOR2  "v_xor_b32 %[d0], %[tlo], %[g0]\n\t" "v_xor_b32 %[d1], %[tlo], %[g1]\n\t"
+#define NVB_PD3_COL0(L) L \
             "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
             "v_add_u32 %[d], %[s0], %[d]\n\t" \
             "v_pk_max_u16 %[h], %[f0], %[d]\n\t" \
@@ -420,17 +481,18 @@ struct PD3 : PairOps {
     static __device__ __forceinline__ void col0(uint32_t& F0, const uint32_t F1, uint32_t& S0, const uint32_t S1, uint32_t& rowkey,
                                                 const uint32_t g0, const uint32_t D, const uint32_t tlo, const uint32_t thi, const uint32_t Z0, const uint32_t K0)
     {
-        uint32_t d, h;
-        if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
-        else                                   asm(NVB_PD3_COL0 : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "s"(D), [k0] "s"(K0));
+        uint32_t d = g0, h;
+        if constexpr ((FORM & PF_SUBLDS) != 0)      asm(NVB_PD3_COL0("") : [f0] "=&v"(F0), [d] "+&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
+                                                                         : [f1] "v"(F1), [s1] "v"(S1), [z0] "s"(Z0), [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
+        else if constexpr ((FORM & PF_KO_PERM) != 0) asm(NVB_PD3_COL0(NVB_PD3_XOR1) : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
+        else if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_COL0(NVB_PD3_PERM1) : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
+        else                                        asm(NVB_PD3_COL0(NVB_PD3_PERM1) : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "s"(D), [k0] "s"(K0));
     }
 
     // PM3::cell2 without E's subtracts: E'(J+1) = max(E'(J), S'(J)).  Ein: E'(i,J), read only (column 1's is S'(i,0), which stays live as
     // the next row's diagonal); E: E'(i,J+2).  Z0, Z1: Z(i,J), Z(i,J+1); K0, K1: K_J, K_(J+1); they and D are scalars, one to an instruction.
     // P: PF_CONST2's pad behind each group of simple ops, or nothing
-#define NVB_PD3_CELL2(P) \
-            "v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t" \
-            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t" \
+#define NVB_PD3_CELL2(L, P) L \
             "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
             "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z1]\n\t" \
             "v_add_u32 %[d0], %[s0], %[d0]\n\t" \
@@ -452,16 +514,19 @@ struct PD3 : PairOps {
                                                  uint32_t& rowkey, const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
-        uint32_t d0, d1, h;
-        if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_CELL2("s_nop 0\n\t") : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
-        else                                   asm(NVB_PD3_CELL2("") : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
+        uint32_t d0 = g0, d1 = g1, h;
+        if constexpr ((FORM & PF_SUBLDS) != 0)
+            asm(NVB_PD3_CELL2("", "s_nop 0\n\t")
+                : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "+&v"(d0), [d1] "+&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
+                : [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_KO_PERM) != 0) asm(NVB_PD3_CELL2(NVB_PD3_XOR2, "s_nop 0\n\t") : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_CELL2(NVB_PD3_PERM2, "s_nop 0\n\t") : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else                                        asm(NVB_PD3_CELL2(NVB_PD3_PERM2, "") : NVB_PD3_CELL2_OUT : NVB_PD3_CELL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
     }
 
     // PM3::tail2 in the column frame: the cell J next to the band's edge (F' = max(S'(i-1,J+1), Z(i,J))) and the last column J + 1
     // (h = max3(E', diagonal, Z(i,J+1)))
-#define NVB_PD3_TAIL2 \
-            "v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t" \
-            "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t" \
+#define NVB_PD3_TAIL2(L) L \
             "v_pk_max_u16 %[f0], %[s1], %[z0]\n\t" \
             "v_add_u32 %[d0], %[s0], %[d0]\n\t" \
             "v_add_u32 %[d1], %[s1], %[d1]\n\t" \
@@ -480,9 +545,14 @@ struct PD3 : PairOps {
                                                  const uint32_t g0, const uint32_t g1, const uint32_t D, const uint32_t tlo, const uint32_t thi,
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
-        uint32_t d0, d1, h, e;
-        if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
-        else                                   asm(NVB_PD3_TAIL2 : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
+        uint32_t d0 = g0, d1 = g1, h, e;
+        if constexpr ((FORM & PF_SUBLDS) != 0)
+            asm(NVB_PD3_TAIL2("")
+                : [f0] "=&v"(F0), [d0] "+&v"(d0), [d1] "+&v"(d1), [h] "=&v"(h), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
+                : [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_KO_PERM) != 0) asm(NVB_PD3_TAIL2(NVB_PD3_XOR2) : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_TAIL2(NVB_PD3_PERM2) : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else                                        asm(NVB_PD3_TAIL2(NVB_PD3_PERM2) : NVB_PD3_TAIL2_OUT : NVB_PD3_TAIL2_IN, [dd] "s"(D), [k0] "s"(K0), [k1] "s"(K1));
     }
 
     template <int BAND, int R, int FORM, int J, int END>
@@ -498,6 +568,22 @@ struct PD3 : PairOps {
     template <int BAND, int R, int FORM, int END>
     struct Cells<BAND, R, FORM, END, END> {
         static __device__ __forceinline__ void run(PairState<BAND>&, const ColumnFrame<BAND>&, const uint32_t Ein, uint32_t& E, uint32_t&, uint32_t, uint32_t) { E = Ein; }
+    };
+
+    // PF_SUBLDS: the same cells on the row's words w[j], which its head has read from the block's table
+    template <int BAND, int R, int FORM, int J, int END>
+    struct SubCells {
+        static __device__ __forceinline__ void run(PairState<BAND>& st, const ColumnFrame<BAND>& fr, const uint32_t Ein, uint32_t& E, uint32_t& rowkey, const uint32_t (&w)[BAND])
+        {
+            uint32_t En;
+            cell2<FORM, J>(st.F[J], st.F[J + 1], st.F[J + 2], st.S[J], st.S[J + 1], st.S[J + 2], Ein, En, rowkey, w[J], w[J + 1], fr.D, 0u, 0u,
+                           fr.z[(2 * R + J) & 15], fr.z[(2 * R + J + 1) & 15], fr.k[J], fr.k[J + 1]);
+            SubCells<BAND, R, FORM, J + 2, END>::run(st, fr, En, E, rowkey, w);
+        }
+    };
+    template <int BAND, int R, int FORM, int END>
+    struct SubCells<BAND, R, FORM, END, END> {
+        static __device__ __forceinline__ void run(PairState<BAND>&, const ColumnFrame<BAND>&, const uint32_t Ein, uint32_t& E, uint32_t&, const uint32_t (&)[BAND]) { E = Ein; }
     };
 
     // the wave's frame before row 0: slot s of the ring holds Z(0, s) = BIAS' + G (2 + s) for the columns row 0's prologue leaves alone and
@@ -516,19 +602,41 @@ struct PD3 : PairOps {
 
     // rk2 (PF_FOLD2): the even row's row key, which waits for the odd row's
     template <int BAND, int R, int FORM>
-    static __device__ __forceinline__ void row(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i, const uint32_t g_new, const uint32_t tlo, const uint32_t thi, uint32_t& rk2)
+    static __device__ __forceinline__ void row(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i, const uint32_t g_new, const uint32_t tlo, const uint32_t thi, uint32_t& rk2,
+                                               const uint32_t* sub = nullptr)
     {
         static_assert(BAND == 15, "a row's zeros, 2 i ... 2 i + BAND - 1, and the two the next row adds fill the ring of 16; columns go two at a time");
         // this row's zeros: Z(i, BAND-2) and Z(i, BAND-1) take the slots of Z(i-1, 0) - G and Z(i-1, 0); scalar adds
         fr.z[(2 * R + BAND - 2) & 15] += fr.step;
         fr.z[(2 * R + BAND - 1) & 15] += fr.step;
         uint32_t rowkey, E;
-        col0<FORM>(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, st.tc[R & 15], fr.D, tlo, thi, fr.z[(2 * R) & 15], fr.k[0]);
-        // 1 <= j <= BAND-3, then BAND-2 and BAND-1
-        Cells<BAND, R, FORM, 1, BAND - 2>::run(st, fr, st.S[0], E, rowkey, tlo, thi);
-        st.tc[(R + BAND - 1) & 15] = g_new;
-        tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
-                              fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        if constexpr ((FORM & PF_SUBLDS) != 0)
+        {
+            // g_new: the entering column word; tlo: the row word; sub: the block's table.  The reads go out in two batches, each in the
+            // order the cells take its words, so the counted waits fall before each cell block: columns 0 ... 7 at the row's head, the
+            // rest behind column 4, into the registers columns 0 ... 4 have given back (fifteen landing registers do not fit 96)
+            constexpr int HEAD = 8, SPLIT = 5;
+            st.tc[(R + BAND - 1) & 15] = g_new;
+            uint32_t w[BAND], Em;
+            #pragma unroll
+            for (int j = 0; j < HEAD; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15]));
+            col0<FORM>(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, w[0], fr.D, 0u, 0u, fr.z[(2 * R) & 15], fr.k[0]);
+            SubCells<BAND, R, FORM, 1, SPLIT>::run(st, fr, st.S[0], Em, rowkey, w);
+            #pragma unroll
+            for (int j = HEAD; j < BAND; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15]));
+            SubCells<BAND, R, FORM, SPLIT, BAND - 2>::run(st, fr, Em, E, rowkey, w);
+            tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, w[BAND - 2], w[BAND - 1], fr.D, 0u, 0u,
+                                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        }
+        else
+        {
+            col0<FORM>(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, st.tc[R & 15], fr.D, tlo, thi, fr.z[(2 * R) & 15], fr.k[0]);
+            // 1 <= j <= BAND-3, then BAND-2 and BAND-1
+            Cells<BAND, R, FORM, 1, BAND - 2>::run(st, fr, st.S[0], E, rowkey, tlo, thi);
+            st.tc[(R + BAND - 1) & 15] = g_new;
+            tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, st.tc[(R + BAND - 2) & 15], g_new, fr.D, tlo, thi,
+                                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        }
         if constexpr ((FORM & PF_FOLD2) != 0)
         {
             // the header comment, "The pair fold": the even row's key moves into the odd row's frame (2 G up), the odd row's takes the
@@ -559,14 +667,26 @@ struct PairRows {
     {
         if ((FORM & PF_KO_BOUND) || i0 + R < M)
         {
-            const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
-            if constexpr (CELL::COLUMN)
+            if constexpr ((FORM & PF_SUBLDS) != 0)
             {
+                // PA / PB hold the block's row words of the even / the odd rows, a byte each, and XT[0] / XT[1] the entering column
+                // words of the even / the odd rows, a nibble each (sub_row_words; the kernel's block loop): both leave here as byte offsets
+                constexpr int K = R >> 1;
+                const uint32_t zw = uint32_t(((R & 1) ? PB : PA) >> (32 * (K >> 2))), xw = XT[R & 1];
+                uint32_t rw = (K & 3) == 0 ? (zw << 2) & 0x3FCu : (zw >> (8 * (K & 3) - 2)) & 0x3FCu;
+                uint32_t cw = K == 0 ? (xw << 2) & 0x3Cu : (xw >> (4 * K - 2)) & 0x3Cu;
+                asm("" : "+v"(rw)); asm("" : "+v"(cw));                               // whole words: the cells' xors take no mask along (a three-source op, and a scalar)
+                CELL::template row<BAND, R, FORM>(st, fr, i0 + R, cw, rw, 0u, rk2, tab);
+            }
+            else if constexpr (CELL::COLUMN)
+            {
+                const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
                 if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, KT[0], KT[1], rk2);
                 else                    CELL::template row<BAND, R, FORM>(st, fr, i0 + R, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u], rk2);
             }
             else
             {
+                const uint32_t g = ((XT[R >> 3] >> (2 * (R & 7))) & 0x00030003u) | CELL::SEL_BASE;
                 if (FORM & PF_KO_TABLE) CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, KT[0], KT[1]);
                 else                    CELL::template row<BAND, R, FORM>(st, i0 + R, D, G, g, tab[uint32_t(PA >> (4 * R)) & 15u], tab[uint32_t(PB >> (4 * R)) & 15u]);
             }
@@ -585,19 +705,31 @@ template <typename CELL, int BAND, int FORM, int END> struct PairRows<CELL, BAND
 // FORM & PF_STREAM: the host has also checked that both word arrays are short enough for GroupStream's 32-bit byte offsets and has
 // picked the instance of the pattern's width and the two byte orders (PF_PAT2, PF_PBE, PF_TBE), so the loop tests none of them; it
 // loads three new words per job and block where fetch16_* loads five.
+// PF_SUBLDS asks the compiler for five waves per SIMD (96 VGPRs), which its landing registers would otherwise pass by two; every other
+// form keeps the default, 1, and the assembly it had.
 constexpr int PAIR_LANES = 128;
 template <int BAND, typename CELL, int FORM>
-__global__ void __launch_bounds__(PAIR_LANES)
+__global__ void __launch_bounds__(PAIR_LANES) __attribute__((amdgpu_waves_per_eu((FORM & PF_SUBLDS) ? 5 : 1)))
 banded_gotoh_pair_kernel(const GotohParams p)
 {
     static_assert(BAND >= 3 && BAND <= 16, "the ring of 16");
-    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0, FOLD2 = (FORM & PF_FOLD2) != 0;
+    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0, FOLD2 = (FORM & PF_FOLD2) != 0, SUBLDS = (FORM & PF_SUBLDS) != 0;
+    static_assert(!(FORM & (PF_SUBLDS | PF_KO_PERM)) || ((FORM & PF_FOLD2) && (FORM & PF_CONST2) == PF_CONST2), "the LDS words and the probe's xor row are forms of the library's row");
+    static_assert(!SUBLDS || !(FORM & (PF_KO_TABLE | PF_KO_PERM)), "the LDS words have no lookup to knock out");
     static_assert(!(FORM & (PF_FOLD2 | PF_CONST2)) || CELL::COLUMN, "the pair fold and the literals are the column frame's");
     static_assert(!FOLD2 || !(FORM & (PF_SINK_KEY | PF_KO_SINK | PF_KO_BOUND)), "the pair fold is the compare-and-select fold's, over the job's own rows");
     static_assert(!(FORM & PF_GE3) || (FORM & PF_CONST2), "|G_e| is the literal form's parameter");
     constexpr bool P4 = !(FORM & PF_PAT2), PBE = (FORM & PF_PBE) != 0, TBE = (FORM & PF_TBE) != 0;     // STREAM only: the host has matched them to the strings
     __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
-    if (threadIdx.x < 16u)
+    __shared__ uint32_t s_sub[256];          // PF_SUBLDS: by sub_index of both jobs' codes nibble ^ symbol: {0, sub(c_B), 0, sub(c_A)}, sub(0) the match byte
+    if constexpr (SUBLDS)
+    {
+        const uint32_t tg = uint32_t(-p.gap_ext * 32);
+        const uint32_t sm = uint32_t((p.match - p.gap_open) * 32) + tg, sx = uint32_t((p.mismatch - p.gap_open) * 32) + tg;
+        for (uint32_t k = threadIdx.x; k < 256u; k += uint32_t(PAIR_LANES))
+            s_sub[k] = (sub_code_a(k) == 0u ? sm : sx) | ((sub_code_b(k) == 0u ? sm : sx) << 16);
+    }
+    else if (threadIdx.x < 16u)
     {
         // (the column frame's diagonal step rises by 2 G where the row frame's rises by G: the table carries the other G)
         const uint32_t tg = CELL::COLUMN ? uint32_t(-p.gap_ext * 32) : 0u;
@@ -635,7 +767,8 @@ banded_gotoh_pair_kernel(const GotohParams p)
         const uint32_t TA = fetch16_2bit(ts[0], tb[0]), TB = fetch16_2bit(ts[1], tb[1]);
         #pragma unroll
         for (int j = 0; j < BAND - 1; ++j)
-            st.tc[j] = CELL::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
+            st.tc[j] = SUBLDS ? (((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 2)) << 2
+                              : CELL::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
     }
 
     // this block's symbols and the cursors behind them (STREAM), or the generic fetches
@@ -674,8 +807,18 @@ banded_gotoh_pair_kernel(const GotohParams p)
             PAn = fetch_pattern16(ps[0], pb[0] + i0 + 16u); PBn = fetch_pattern16(ps[1], pb[1] + i0 + 16u);
             TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1); TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
         }
-        const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
-        PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, PA, PB, XT, s_tab, KT, rk2);
+        if constexpr (SUBLDS)
+        {
+            uint64_t RE, RO;
+            sub_row_words(PA, PB, RE, RO);
+            const uint32_t XT[2] = { sub_bfi(0x33333333u, TA, TB << 2), sub_bfi(0x33333333u, TA >> 2, TB) };   // the entering column words, nibble m: t_A | t_B << 2 of rows 2 m / 2 m + 1
+            PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, RE, RO, XT, s_sub, KT, rk2);
+        }
+        else
+        {
+            const uint32_t XT[2] = { (TA & 0xFFFFu) | (TB << 16), (TA >> 16) | (TB & 0xFFFF0000u) };
+            PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, PA, PB, XT, s_tab, KT, rk2);
+        }
         if (FORM & PF_KO_FETCH)
         {
             PA = (PA << 4) | (PA >> 60); PB = (PB << 8) | (PB >> 56);
@@ -711,8 +854,8 @@ hipError_t launch_band_pair(const GotohParams& p, hipStream_t stream)
     return hipGetLastError();
 }
 
-// The library's instances (NVB_PAIR_INSTANCES) are compiled in banded_gotoh_pair_b15.hip and banded_gotoh_pair_b15_lit.hip.  A translation unit that launches them and must not compile them again defines NVB_PAIR_EXTERN before
-// it includes this header: banded_gotoh.hip does; the two instantiation files, and tools/pair_row_probe.hip with its own forms, do not
+// The library's instances (NVB_PAIR_INSTANCES) are compiled in banded_gotoh_pair_b15.hip, banded_gotoh_pair_b15_lit.hip and banded_gotoh_pair_b15_sub.hip.  A translation unit that launches them and must not compile them again defines NVB_PAIR_EXTERN before
+// it includes this header: banded_gotoh.hip does; the three instantiation files, and tools/pair_row_probe.hip with its own forms, do not
 #ifdef NVB_PAIR_EXTERN
 #define NVB_DECL(CELL, F) extern template hipError_t launch_band_pair<15, CELL, (F)>(const GotohParams&, hipStream_t);
 NVB_PAIR_INSTANCES(NVB_DECL)

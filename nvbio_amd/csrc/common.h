@@ -11,7 +11,7 @@ namespace nvb {
 // thread-local name of the last kernel variant launched (introspection for tests/bench)
 extern thread_local const char* g_last_kernel;
 // the last banded launch, if it took the two-jobs-per-lane form (banded_gotoh_pair.h): what nvbio_hip_last_kernel_detail, _cell,
-// _fetch, _frame, _row and _const answer, which is "" unless `kernel` is still g_last_kernel
+// _fetch, _frame, _row, _const and _sub answer, which is "" unless `kernel` is still g_last_kernel
 struct PairLaunch {
     const char* kernel = nullptr;   // the g_last_kernel value of that launch, or NULL
     const char* cell   = "";        // the cell it ran, "u16" or "max3"
@@ -19,13 +19,14 @@ struct PairLaunch {
     const char* frame  = "";        // the frame its cell holds, "column" (PD3) or "row" (PM3, P16)
     const char* row    = "";        // the row around its cells, "fold2" (PD3 by default: the sink folded once per two rows) or "plain"
     const char* consts = "";        // where its cell keeps the key constants K_j, "literal" (PD3 with the pair fold by default, |G_e| <= 3) or "scalar"
+    const char* sub    = "";        // where its cell's substitution words come from, "lds" (one LDS read per cell: the literal form by default) or "perm"
 };
 extern thread_local PairLaunch g_last_pair;
 
 // Test switches (include/nvbio_hip.h, "Test switches"): alternative executions of the same results.  Each is an atomic int, seeded ONCE
 // from the environment variable of the same name (std::call_once) and changed afterwards only through nvbio_hip_set_test_switch --
 // no getenv on the launch paths, which run on several driver threads at a time.
-enum TestSwitch { SW_FORCE_32BIT = 0, SW_NO_STAGING, SW_FULL_GENERIC, SW_ED_SWEEP, SW_FULL_SINGLE_JOB, SW_FULL_ROWS, SW_TRACEBACK_LANES, SW_SELECT_LANES, SW_BANDED_PAIR, SW_PAIR_ROW, SW_PAIR_CONST, SW_COUNT };
+enum TestSwitch { SW_FORCE_32BIT = 0, SW_NO_STAGING, SW_FULL_GENERIC, SW_ED_SWEEP, SW_FULL_SINGLE_JOB, SW_FULL_ROWS, SW_TRACEBACK_LANES, SW_SELECT_LANES, SW_BANDED_PAIR, SW_PAIR_ROW, SW_PAIR_CONST, SW_PAIR_SUB, SW_COUNT };
 int test_switch(TestSwitch which);       // the switch's integer value; 0 = default execution
 
 // ---------------------------------------------------------------------------

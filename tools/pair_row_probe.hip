@@ -7,8 +7,10 @@
 // A knock-out takes one part of the row away and keeps its inputs live (PairForm, PF_KO_*); what it prints is a time, never a result.
 // The forms that do compute results print a checksum of scores and sinks, which must be the same for all of them.
 // The last rows are the column frame's row with its sink folded once per two rows (PF_FOLD2), and that row with the cell's wave-uniform
-// constants in scalar registers (const-s) and as literals with the pad (PF_CONST2, const-klit-pad), which the library launches.  The
-// forms that were measured beside them and are gone have their figures in profiles/banded_pair/README.md.
+// constants in scalar registers (const-s) and as literals with the pad (PF_CONST2, const-klit-pad), and on that row the two sub-* rows:
+// the knock-out with a v_xor_b32 in each v_perm_b32's place (PF_KO_PERM, the ceiling of the lookup's class change) and the substitution
+// words read from LDS (PF_SUBLDS, sub-lds), which the library launches.  The forms that were measured beside them and are gone have
+// their figures in profiles/banded_pair/README.md.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/pair_row_probe.hip -o tools/pair_row_probe
 //   tools/pair_row_probe [jobs = 10000000] [timed launches = 10] [only the variants whose names begin with this]
@@ -107,6 +109,11 @@ static const Variant VARIANTS[] = {
     { "const-s",    "col-fold2 once more: D and K_j in scalar registers",              COLF(STREAMED | PF_FOLD2), READ, true },
     { "const-klit-pad", "col-fold2, K_j and 2 G literals, s_nop pads (the library's launch)", COLF(STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1), READ, true },
     { "const-s'",   "const-s once more (the run's drift)",                             COLF(STREAMED | PF_FOLD2), READ, true },
+    // where the substitution words come from, on const-klit-pad's row: the ceiling of the lookup's class change (a knock-out), and the
+    // words read from LDS, one ds_read_b32 per cell, whose checksum must be const-klit-pad's
+    { "sub-xor",    "const-klit-pad, a v_xor_b32 for each v_perm_b32, table reads kept", COLF(STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1 | PF_KO_PERM), READ, false },
+    { "sub-lds",    "const-klit-pad, substitution words from LDS (PF_SUBLDS)",         COLF(STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1 | PF_SUBLDS), READ, true },
+    { "sub-perm'",  "const-klit-pad once more (the run's drift)",                      COLF(STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1), READ, true },
 };
 
 int main(int argc, char** argv)
