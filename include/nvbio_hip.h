@@ -1061,6 +1061,48 @@ int nvbio_hip_suffix_sort_host(const uint32_t* words, uint32_t bits, uint32_t bi
 int nvbio_hip_bwt_host(const uint32_t* words, uint32_t bits, uint32_t big_endian, uint64_t n, uint32_t sa_int, uint32_t* bwt_words_out,
                        uint32_t* primary_out, uint32_t* ssa_out, uint32_t* sa_out, int32_t n_threads);
 
+/* ---- Suffix sorting and BWT of a set of 2-bit strings (nvbio/sufsort/sufsort.h: cuda::suffix_sort(string_set, handler) and
+ * cuda::bwt<SYMBOL_SIZE,BIG_ENDIAN>(ConcatenatedStringSet, handler), for a set that fits the device).
+ * set: n_strings strings in any of the forms nvbio_hip_string_set allows (a length array, or fixed_length; begin offsets in any order,
+ * at any position of a word, overlapping or not); bits must be 2.  The slots of the set are the pairs (s, p), 0 <= p <= length[s]: the
+ * suffix of string s from symbol p on, the empty suffix p == length[s] included.  Slot (s, p) has the global suffix index
+ * g = cum[s - 1] + p, where cum[s] = the inclusive sum of length + 1 and cum[-1] = 0; n_suffixes = cum[n_strings - 1] is passed by the
+ * caller, whose buffers it sizes, and checked.  1 <= n_strings <= n_suffixes <= 0xFFFFFFFE.
+ * Order: by the suffix's symbols, a suffix that is a proper prefix of another first ($ < A); equal suffixes by ascending string id.
+ * Rows 0 .. n_strings - 1 are therefore the empty suffixes in id order.
+ * nvbio_hip_set_suffix_sort: suffixes_out[row] = the global index on that row; string_ids_out[g] (may be NULL) = the string of global
+ * index g; cum_lengths_out (may be NULL) = cum.
+ * nvbio_hip_set_bwt: bwt_out[row] = symbol p - 1 of string s for the slot (s, p) on that row, 255 ('$') where p == 0; dollar_rows_out =
+ * the n_strings rows that hold 255, ascending, dollar_ids_out = the string each of them starts; suffixes_out (may be NULL) = the pair
+ * (p, s) of every row, the reference's uint2 (x = suffix, y = string).
+ * temp: device scratch of the matching _temp_bytes(n_suffixes, n_strings) bytes; nothing is allocated inside.  Layout: the plain
+ * sorter's seven arrays over n_suffixes (36 bytes a slot) | string_ids (4 bytes a slot) | cum as 64-bit sums (8 bytes a string) |
+ * rocPRIM's scratch; nvbio_hip_set_bwt puts the sorted slots (4 bytes a slot) in front: 40 and 44 bytes a slot.
+ * Both entries wait for the stream once per sorting round and have finished when they return.  A null pointer, bits != 2, a count out
+ * of range or too little temp return hipErrorInvalidValue and launch nothing.  So does an n_suffixes that is not the sum of
+ * fixed_length + 1; with a length array the sum is known on the device only: the first round runs inside the scratch, writes nothing
+ * to the outputs unless the sum is n_suffixes, and its wait brings the sum to the host, where a wrong n_suffixes returns
+ * hipErrorInvalidValue with the outputs untouched.  nvbio_hip_suffix_sort_last_rounds reports the rounds of a set call too.
+ * The host twins take host pointers and a thread count, and return the same bytes; they take n_strings <= 0xFFFFFFFB (their first
+ * ranks, n_strings + 1 + symbol, are 32-bit words) and return hipErrorInvalidValue above that. */
+uint64_t nvbio_hip_set_suffix_sort_temp_bytes(uint64_t n_suffixes, uint32_t n_strings);
+int nvbio_hip_set_suffix_sort(const nvbio_hip_string_set* set /* host struct, device arrays; bits must be 2 */,
+                              uint32_t n_strings, uint64_t n_suffixes,
+                              uint32_t* suffixes_out   /* [n_suffixes] global suffix indices in sorted order */,
+                              uint32_t* string_ids_out /* [n_suffixes] string of global index g; may be NULL */,
+                              uint32_t* cum_lengths_out/* [n_strings] inclusive sums of length + 1; may be NULL */,
+                              void* temp, uint64_t temp_bytes, void* stream);
+uint64_t nvbio_hip_set_bwt_temp_bytes(uint64_t n_suffixes, uint32_t n_strings);
+int nvbio_hip_set_bwt(const nvbio_hip_string_set* set, uint32_t n_strings, uint64_t n_suffixes,
+                      uint8_t*  bwt_out        /* [n_suffixes], 255 = '$' */,
+                      uint32_t* dollar_rows_out/* [n_strings] */, uint32_t* dollar_ids_out /* [n_strings] */,
+                      uint32_t* suffixes_out   /* [2 * n_suffixes]: (p, s) pairs in sorted order; may be NULL */,
+                      void* temp, uint64_t temp_bytes, void* stream);
+int nvbio_hip_set_suffix_sort_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint64_t n_suffixes, uint32_t* suffixes_out,
+                                   uint32_t* string_ids_out, uint32_t* cum_lengths_out, int32_t n_threads);
+int nvbio_hip_set_bwt_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint64_t n_suffixes, uint8_t* bwt_out,
+                           uint32_t* dollar_rows_out, uint32_t* dollar_ids_out, uint32_t* suffixes_out, int32_t n_threads);
+
 /* Device-memory helpers for host code that has no HIP headers (the C++ host layer in
  * include/nvbio_hip/ uses them where the reference uses thrust::device_vector).
  * kind: 1 = host->device, 2 = device->host, 3 = device->device. */

@@ -9,19 +9,34 @@
 //                                                               '$' removed and the symbols after it shifted back (sufsort_inl.h:239-265,
 //                                                               sufsort_utils.h:358-366, :412); the primary counts the empty suffix's row
 //
+//   cuda::suffix_sort(string_set, handler, params)              the suffixes of every string of a device-side set, the empty ones
+//                                                               included, sorted; handler.process(n_suffixes, d_suffixes, d_string_ids,
+//                                                               d_cum_lengths) is called once, with device pointers (sufsort.h:207-233)
+//   SetBWTHandler                                               the base of the string-set BWT handlers (sufsort_utils.h:57-81)
+//   cuda::bwt<SYMBOL_SIZE,BIG_ENDIAN>(string_set, handler, params)
+//                                                               the BWT of a device-side packed-concatenated set; handler.process(
+//                                                               n_suffixes, h_bwt, n_dollars, h_dollar_pos, h_dollar_ids) is called once,
+//                                                               with host arrays: one byte a row, 255 = '$', the '$' rows as absolute
+//                                                               positions and their string ids as uint64 (what DollarExtractor::extract
+//                                                               hands on, sufsort_priv.cu:453-527; the reference calls it once per batch)
+//
 // `string` is a device-side iterator over a 2-bit alphabet.  A PackedStream over a word pointer that starts on a word boundary goes to
 // nvbio_hip_suffix_sort / nvbio_hip_bwt (include/nvbio_hip.h) in place; any other 2-bit iterator is packed into
-// big-endian words first, then takes the same call.  Wider alphabets throw.  blockwise_suffix_sort, the string-set sorters and
-// large_bwt are not provided.  Needs a translation unit compiled by hipcc and linked with libnvbio_hip.
+// big-endian words first, then takes the same call.  Wider alphabets throw.  A string set is a ConcatenatedStringSet over a 2-bit
+// PackedStream on a word pointer with device offsets; it goes to nvbio_hip_set_suffix_sort / nvbio_hip_set_bwt in place, at whatever
+// symbol its stream starts.  blockwise_suffix_sort, large_bwt (sets that do not fit the device), the file handlers and 4-bit sets are
+// not provided.  Needs a translation unit compiled by hipcc and linked with libnvbio_hip.
 #pragma once
 #include "../basic/types.h"
 #include "../basic/packedstream.h"
 #include "../basic/packed_view.h"
 #include "../basic/vector.h"
+#include "../strings/string_set.h"
 #include "../../../../nvbio_hip.h"
 #include <hip/hip_runtime.h>
 #include <stdexcept>
 #include <string>
+#include <vector>
 
 namespace nvbio {
 
@@ -157,7 +172,99 @@ inline void check_length(const uint64 n)
     if (n == 0u || n > 0xFFFFFFFEull) throw std::runtime_error("nvbio::cuda sufsort: the string must hold between 1 and 2^32 - 2 symbols");
 }
 
+/// begin[s] = first + offsets[s] and length[s] of every string of a concatenated set, as the C-ABI takes them; ends[0 .. 1] = the
+/// first and the last offset
+template <typename offset_iterator>
+__global__ void set_offsets_kernel(const uint32 n_strings, const offset_iterator offsets, const uint64 first, uint64* begin, uint32* length, uint64* ends)
+{
+    const uint32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_strings) return;
+    const uint64 b = uint64(offsets[i]), e = uint64(offsets[i + 1u]);
+    begin[i]  = first + b;
+    length[i] = uint32(e - b);
+    if (i == 0u) ends[0] = b;
+    if (i + 1u == n_strings) ends[1] = e;
+}
+
+static __global__ void widen_kernel(const uint32 n, const uint32* in, uint64* out)
+{
+    const uint32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i < n) out[i] = in[i];
+}
+
+/// a device-side ConcatenatedStringSet over a 2-bit PackedStream as the C-ABI's nvbio_hip_string_set, its strings' words in place
+template <typename string_set_type>
+struct packed_set
+{
+    typedef typename string_set_type::symbol_iterator                stream_type;
+    typedef nvbio::priv::packed_stream_where<stream_type>            where_type;
+
+    explicit packed_set(const string_set_type& string_set) : n_strings(string_set.size()), n_suffixes(0), arrays(nullptr)
+    {
+        init(string_set, std::integral_constant<bool, where_type::ok && where_type::BITS == 2u>());
+    }
+    ~packed_set() { delete arrays; }
+    packed_set(const packed_set&) = delete;
+    packed_set& operator=(const packed_set&) = delete;
+
+    void init(const string_set_type&, std::false_type) { throw std::runtime_error("nvbio::cuda sufsort: only sets of 2-bit packed strings over 32-bit words are supported"); }
+    void init(const string_set_type& string_set, std::true_type)
+    {
+        if (n_strings == 0u) throw std::runtime_error("nvbio::cuda sufsort: the set must hold at least one string");
+        uint64 word0; uint32 first;
+        where_type::where(string_set.base_string(), word0, first);
+        // begin (8 N) | ends (16) | length (4 N)
+        arrays = new scratch(uint64(n_strings) * 12u + 16u);
+        uint64* begin  = arrays->template as<uint64>();
+        uint64* ends   = begin + n_strings;
+        uint32* length = reinterpret_cast<uint32*>(ends + 2);
+        hipLaunchKernelGGL((set_offsets_kernel<typename string_set_type::offset_iterator>), dim3((n_strings + 255u) / 256u), dim3(256), 0, 0,
+                           n_strings, string_set.offsets(), uint64(first), begin, length, ends);
+        check(hipGetLastError(), "set_offsets_kernel");
+        uint64 h_ends[2] = { 0u, 0u };
+        check(hipMemcpy(h_ends, ends, 16u, hipMemcpyDeviceToHost), "hipMemcpy");
+        n_suffixes = (h_ends[1] - h_ends[0]) + n_strings;
+        if (n_suffixes > 0xFFFFFFFEull) throw std::runtime_error("nvbio::cuda sufsort: the set must hold at most 2^32 - 2 symbols and strings together");
+        set.words      = reinterpret_cast<const uint32*>(uintptr_t(word0) * 4u);
+        set.n_words    = (uint64(first) + h_ends[1] + 15u) / 16u;
+        set.bits       = 2u;
+        set.big_endian = where_type::BE ? 1u : 0u;
+        set.begin      = begin;
+        set.length     = length;
+        set.fixed_length = 0u;
+        set._pad       = 0u;
+    }
+
+    nvbio_hip_string_set set;
+    uint32               n_strings;
+    uint64               n_suffixes;
+    scratch*             arrays;
+};
+
 } // namespace sufsort
+
+/// base virtual interface used by all string-set BWT handlers (sufsort_utils.h:57-81)
+struct SetBWTHandler
+{
+    virtual ~SetBWTHandler() {}
+
+    /// process a batch of BWT symbols, packed
+    virtual void process(
+        const uint32  n_suffixes,
+        const uint32  bits_per_symbol,
+        const uint32* bwt,
+        const uint32  n_dollars,
+        const uint64* dollar_pos,
+        const uint64* dollar_ids) {}
+
+    /// process a batch of BWT symbols, one byte each
+    virtual void process(
+        const uint32  n_suffixes,
+        const uint8*  bwt,
+        const uint32  n_dollars,
+        const uint64* dollar_pos,
+        const uint64* dollar_ids) {}
+};
 
 namespace cuda {
 
@@ -227,6 +334,56 @@ typename string_type::index_type find_primary(
     uint32 primary = 0;
     sufsort::check(nvbio_hip_bwt(text.words, 2u, text.big_endian, n, 0u, words.as<uint32>(), &primary, nullptr, nullptr, temp.ptr, tb, nullptr), "nvbio_hip_bwt");
     return typename string_type::index_type(primary);
+}
+
+/// Sort the suffixes of all the strings in the given string set; the handler is a SetSuffixOutputHandler (sufsort.h:207-233)
+template <typename string_set_type, typename output_handler>
+void suffix_sort(
+    const string_set_type&   string_set,
+          output_handler&    output,
+    BWTParams*               params = NULL)
+{
+    (void)params;
+    sufsort::packed_set<string_set_type> set(string_set);
+    const uint64 n = set.n_suffixes;
+    const uint64 tb = nvbio_hip_set_suffix_sort_temp_bytes(n, set.n_strings);
+    sufsort::scratch temp(tb);
+    sufsort::scratch out(n * 8u + uint64(set.n_strings) * 4u);           // suffixes | string ids | cumulative lengths
+    uint32* d_suffixes = out.as<uint32>();
+    sufsort::check(nvbio_hip_set_suffix_sort(&set.set, set.n_strings, n, d_suffixes, d_suffixes + n, d_suffixes + 2u * n, temp.ptr, tb, nullptr), "nvbio_hip_set_suffix_sort");
+    output.process(uint32(n), d_suffixes, d_suffixes + n, d_suffixes + 2u * n);
+}
+
+/// Build the bwt of a device-side string set; the handler is a SetBWTHandler
+template <uint32 SYMBOL_SIZE, bool BIG_ENDIAN, typename storage_type, typename output_handler>
+void bwt(
+    const ConcatenatedStringSet<
+        PackedStream<storage_type,uint8,SYMBOL_SIZE,BIG_ENDIAN,uint64>,
+        uint64*>                    string_set,
+        output_handler&             output,
+        BWTParams*                  params = NULL)
+{
+    typedef ConcatenatedStringSet<PackedStream<storage_type,uint8,SYMBOL_SIZE,BIG_ENDIAN,uint64>, uint64*> string_set_type;
+    (void)params;
+    if (SYMBOL_SIZE != 2u) throw std::runtime_error("nvbio::cuda sufsort: only 2-bit alphabets are supported");
+    sufsort::packed_set<string_set_type> set(string_set);
+    const uint64 n = set.n_suffixes;
+    const uint32 N = set.n_strings;
+    const uint64 tb = nvbio_hip_set_bwt_temp_bytes(n, N);
+    sufsort::scratch temp(tb);
+    // dollar rows and ids as 64-bit (16 N) | the same as the entry writes them (8 N) | bwt (n)
+    sufsort::scratch out(uint64(N) * 24u + n);
+    uint64* d_pos64 = out.as<uint64>();
+    uint32* d_rows  = reinterpret_cast<uint32*>(d_pos64 + 2u * uint64(N));
+    uint8*  d_bwt   = reinterpret_cast<uint8*>(d_rows + 2u * uint64(N));
+    sufsort::check(nvbio_hip_set_bwt(&set.set, N, n, d_bwt, d_rows, d_rows + N, nullptr, temp.ptr, tb, nullptr), "nvbio_hip_set_bwt");
+    hipLaunchKernelGGL(sufsort::widen_kernel, dim3((2u * N + 255u) / 256u), dim3(256), 0, 0, 2u * N, d_rows, d_pos64);
+    sufsort::check(hipGetLastError(), "widen_kernel");
+    std::vector<uint8>  h_bwt(n);
+    std::vector<uint64> h_dollars(2u * uint64(N));
+    sufsort::check(hipMemcpy(h_bwt.data(), d_bwt, n, hipMemcpyDeviceToHost), "hipMemcpy");
+    sufsort::check(hipMemcpy(h_dollars.data(), d_pos64, uint64(N) * 16u, hipMemcpyDeviceToHost), "hipMemcpy");
+    output.process(uint32(n), h_bwt.data(), N, h_dollars.data(), h_dollars.data() + N);
 }
 
 } // namespace cuda

@@ -6,8 +6,15 @@
 //   suffix_sort(text, sa)        sa: n + 1 rows, sa[0] = n, a suffix that is a proper prefix of another first
 //   bwt(text, sa_int, out)       the BWT with the '$' row dropped (big-endian words, what nvbio_hip_build_bwt_occ takes), the primary,
 //                                and on request the sampled and the whole suffix array
+//
+// and of the same module's string-set front door, thin callers of nvbio_hip_set_suffix_sort / nvbio_hip_set_bwt:
+//
+//   set_slot_count(set)                      the set's slots: its symbols + its strings (every string has an empty suffix too)
+//   set_suffix_sort(set, n_suffixes, out)    the global suffix indices in sorted order, the string of every index, the cumulative lengths
+//   set_bwt(set, n_suffixes, out)            one byte a row, 255 = '$', the '$' rows and their strings, on request the (position, string) pairs
 #pragma once
 #include "types.h"
+#include "strings.h"
 
 namespace nvbio {
 namespace hip {
@@ -69,6 +76,80 @@ inline void bwt(const PackedTextView<BE>& text, const uint32 sa_int, BWTResult& 
 {
     device_vector<uint8> temp;
     bwt(text, sa_int, out, temp, want_ssa, want_sa, stream);
+}
+
+/// the slots of a 2-bit string set, the n_suffixes of the calls below: the sum of length + 1 (one copy of the lengths to the host, unless
+/// they are fixed)
+template <bool BE>
+inline uint64 set_slot_count(const PackedStringSetView<2, BE>& set, void* stream = nullptr)
+{
+    if (!set.m_length) return uint64(set.size()) * (uint64(set.m_fixed_length) + 1u);
+    std::vector<uint32> len(set.size());
+    hip_check(nvbio_hip_memcpy(len.data(), set.m_length, uint64(set.size()) * 4u, 2, stream), "nvbio_hip_memcpy(d2h)");
+    hip_check(nvbio_hip_stream_synchronize(stream), "nvbio_hip_stream_synchronize");
+    uint64 n = set.size();
+    for (size_t i = 0; i < len.size(); ++i) n += len[i];
+    return n;
+}
+
+/// what set_suffix_sort() returns
+struct SetSuffixSortResult
+{
+    device_vector<uint32>  suffixes;       ///< n_suffixes global suffix indices, in sorted order
+    device_vector<uint32>  string_ids;     ///< the string of every global index
+    device_vector<uint32>  cum_lengths;    ///< the inclusive sums of length + 1: string s owns the indices [cum_lengths[s - 1], cum_lengths[s])
+};
+
+/// what set_bwt() returns
+struct SetBWTResult
+{
+    device_vector<uint8>   bwt;            ///< n_suffixes bytes: the symbol before the suffix on each row, 255 where it is a whole string
+    device_vector<uint32>  dollar_rows;    ///< the rows that hold 255, ascending: one per string
+    device_vector<uint32>  dollar_ids;     ///< the string each of them starts
+    device_vector<uint32>  suffixes;       ///< 2 * n_suffixes: the (position, string) of every row (empty unless asked for)
+};
+
+/// Sort the suffixes of all the strings of `set`, the empty ones included; a proper prefix first, equal suffixes by string id.
+/// `temp` is the call's scratch, kept by the caller between calls.  A wrong n_suffixes throws.
+template <bool BE>
+inline void set_suffix_sort(const PackedStringSetView<2, BE>& set, const uint64 n_suffixes, SetSuffixSortResult& out, device_vector<uint8>& temp, void* stream = nullptr)
+{
+    const uint64 tb = nvbio_hip_set_suffix_sort_temp_bytes(n_suffixes, set.size());
+    if (temp.size() < tb) temp.resize(tb);
+    out.suffixes.resize(n_suffixes);
+    out.string_ids.resize(n_suffixes);
+    out.cum_lengths.resize(set.size());
+    const nvbio_hip_string_set s = set.abi();
+    hip_check(nvbio_hip_set_suffix_sort(&s, set.size(), n_suffixes, out.suffixes.data(), out.string_ids.data(), out.cum_lengths.data(), temp.data(), temp.size(), stream),
+              "nvbio_hip_set_suffix_sort");
+}
+template <bool BE>
+inline void set_suffix_sort(const PackedStringSetView<2, BE>& set, const uint64 n_suffixes, SetSuffixSortResult& out, void* stream = nullptr)
+{
+    device_vector<uint8> temp;
+    set_suffix_sort(set, n_suffixes, out, temp, stream);
+}
+
+/// The BWT of the set, its '$' rows and (want_suffixes) the (position, string) pair of every row
+template <bool BE>
+inline void set_bwt(const PackedStringSetView<2, BE>& set, const uint64 n_suffixes, SetBWTResult& out, device_vector<uint8>& temp,
+                    const bool want_suffixes = false, void* stream = nullptr)
+{
+    const uint64 tb = nvbio_hip_set_bwt_temp_bytes(n_suffixes, set.size());
+    if (temp.size() < tb) temp.resize(tb);
+    out.bwt.resize(n_suffixes);
+    out.dollar_rows.resize(set.size());
+    out.dollar_ids.resize(set.size());
+    if (want_suffixes) out.suffixes.resize(2u * n_suffixes);
+    const nvbio_hip_string_set s = set.abi();
+    hip_check(nvbio_hip_set_bwt(&s, set.size(), n_suffixes, out.bwt.data(), out.dollar_rows.data(), out.dollar_ids.data(),
+                                want_suffixes ? out.suffixes.data() : nullptr, temp.data(), temp.size(), stream), "nvbio_hip_set_bwt");
+}
+template <bool BE>
+inline void set_bwt(const PackedStringSetView<2, BE>& set, const uint64 n_suffixes, SetBWTResult& out, const bool want_suffixes = false, void* stream = nullptr)
+{
+    device_vector<uint8> temp;
+    set_bwt(set, n_suffixes, out, temp, want_suffixes, stream);
 }
 
 } // namespace hip

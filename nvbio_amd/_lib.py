@@ -34,6 +34,8 @@ SYMBOLS = [
     "nvbio_hip_build_bwt_occ_temp_bytes", "nvbio_hip_build_bwt_occ",
     "nvbio_hip_suffix_sort_temp_bytes", "nvbio_hip_suffix_sort", "nvbio_hip_suffix_sort_last_rounds", "nvbio_hip_bwt_temp_bytes", "nvbio_hip_bwt",
     "nvbio_hip_suffix_sort_host", "nvbio_hip_bwt_host",
+    "nvbio_hip_set_suffix_sort_temp_bytes", "nvbio_hip_set_suffix_sort", "nvbio_hip_set_bwt_temp_bytes", "nvbio_hip_set_bwt",
+    "nvbio_hip_set_suffix_sort_host", "nvbio_hip_set_bwt_host",
     "nvbio_hip_device_malloc", "nvbio_hip_device_free", "nvbio_hip_device_free_ordered", "nvbio_hip_device_free_after", "nvbio_hip_device_trim", "nvbio_hip_device_mem_info", "nvbio_hip_memcpy", "nvbio_hip_memset",
     "nvbio_hip_stream_synchronize", "nvbio_hip_stream_query", "nvbio_hip_host_malloc", "nvbio_hip_host_free", "nvbio_hip_stream_create", "nvbio_hip_stream_destroy",
     "nvbio_hip_comm_available", "nvbio_hip_device_count", "nvbio_hip_set_device", "nvbio_hip_get_device", "nvbio_hip_comm_unique_id", "nvbio_hip_comm_init_rank",
@@ -239,6 +241,14 @@ def lib():
         L.nvbio_hip_bwt.argtypes = [vp, u32, u32, u64, u32, vp, P(u32), vp, vp, vp, u64, vp]
         L.nvbio_hip_suffix_sort_host.argtypes = [vp, u32, u32, u64, vp, i32]
         L.nvbio_hip_bwt_host.argtypes = [vp, u32, u32, u64, u32, vp, P(u32), vp, vp, i32]
+        L.nvbio_hip_set_suffix_sort_temp_bytes.argtypes = [u64, u32]
+        L.nvbio_hip_set_suffix_sort_temp_bytes.restype = u64
+        L.nvbio_hip_set_suffix_sort.argtypes = [P(StringSetStruct), u32, u64, vp, vp, vp, vp, u64, vp]
+        L.nvbio_hip_set_bwt_temp_bytes.argtypes = [u64, u32]
+        L.nvbio_hip_set_bwt_temp_bytes.restype = u64
+        L.nvbio_hip_set_bwt.argtypes = [P(StringSetStruct), u32, u64, vp, vp, vp, vp, vp, u64, vp]
+        L.nvbio_hip_set_suffix_sort_host.argtypes = [P(StringSetStruct), u32, u64, vp, vp, vp, i32]
+        L.nvbio_hip_set_bwt_host.argtypes = [P(StringSetStruct), u32, u64, vp, vp, vp, vp, i32]
         L.nvbio_hip_comm_unique_id.argtypes = [vp]
         L.nvbio_hip_comm_init_rank.argtypes = [P(vp), C.c_int, C.c_int, vp]
         L.nvbio_hip_comm_init_all.argtypes = [vp, C.c_int, vp]

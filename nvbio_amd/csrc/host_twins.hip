@@ -484,3 +484,111 @@ NVB_API int nvbio_hip_bwt_host(const uint32_t* words, uint32_t bits, uint32_t bi
     }
     return hipSuccess;
 }
+
+// ---- suffix sorting and BWT of a set of 2-bit strings (sufsort.hip, the set entries): prefix doubling with std::sort over the slots, each
+// string's empty suffix a terminator of its own that sorts by string id below every symbol -- the definition, and so the same bytes ----
+namespace {
+
+struct SetSlots
+{
+    std::vector<uint64> cum;         // inclusive sums of length + 1
+    std::vector<uint32> sid;         // the string of every slot
+};
+
+inline uint32 set_length(const nvbio_hip_string_set* set, const uint32 s) { return set->length ? set->length[s] : set->fixed_length; }
+
+inline int set_sufsort_args(const nvbio_hip_string_set* set, const uint32 n_strings, const uint64 n)
+{
+    if (!set || !set->words || !set->begin || set->bits != 2u) return hipErrorInvalidValue;
+    if (n_strings == 0u || n_strings > n || n > 0xFFFFFFFEull) return hipErrorInvalidValue;
+    if (n_strings > 0xFFFFFFFBu) return hipErrorInvalidValue;          // the first ranks, up to n_strings + 4, are 32-bit words
+    return hipSuccess;
+}
+
+/// rows[row] = the global index of the slot on that row; hipErrorInvalidValue when the lengths do not add up to n
+int set_suffix_sort_host(const nvbio_hip_string_set* set, const uint32 N, const uint64 n, SetSlots& slots, uint32* rows, const int threads)
+{
+    slots.cum.resize(N);
+    uint64 total = 0;
+    for (uint32 s = 0; s < N; ++s) { total += uint64(set_length(set, s)) + 1u; slots.cum[s] = total; }
+    if (total != n) return hipErrorInvalidValue;
+    slots.sid.resize(n);
+    std::vector<uint32> rank(n), next(n), term(n);       // term: the slot of the string's empty suffix
+    std::vector<uint64> key(n);
+    const uint32 be = set->big_endian ? 1u : 0u;
+    #pragma omp parallel for schedule(dynamic, 256) num_threads(threads)
+    for (int64 s = 0; s < int64(N); ++s)
+    {
+        const uint64 first = s ? slots.cum[s - 1] : 0u, last = slots.cum[s] - 1u;
+        for (uint64 g = first; g <= last; ++g)
+        {
+            slots.sid[g] = uint32(s);
+            term[g] = uint32(last);
+            rows[g] = uint32(g);
+            rank[g] = g == last ? uint32(s) + 1u : N + 1u + text_symbol(set->words, be, set->begin[s] + (g - first));
+        }
+    }
+    // the first key holds an initial rank, which may need all 32 bits beside the next slot's; later ranks are group numbers <= n
+    for (uint64 h = 1;; h *= 2u)
+    {
+        #pragma omp parallel for schedule(static) num_threads(threads)
+        for (int64 g = 0; g < int64(n); ++g)
+            key[g] = (uint64(rank[g]) << 32) | (uint64(g) + h <= term[g] ? rank[uint64(g) + h] : 0u);
+        std::sort(rows, rows + n, [&](const uint32 a, const uint32 b) { return key[a] < key[b]; });
+        uint32 groups = 0;
+        for (uint64 k = 0; k < n; ++k)
+        {
+            if (k == 0 || key[rows[k]] != key[rows[k - 1u]]) ++groups;
+            next[rows[k]] = groups;
+        }
+        rank.swap(next);
+        if (groups == n) return hipSuccess;
+    }
+}
+
+} // anonymous namespace
+
+NVB_API int nvbio_hip_set_suffix_sort_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint64_t n_suffixes, uint32_t* suffixes_out,
+                                           uint32_t* string_ids_out, uint32_t* cum_lengths_out, int32_t n_threads)
+{
+    if (int e = set_sufsort_args(set, n_strings, n_suffixes)) return e;
+    if (!suffixes_out) return hipErrorInvalidValue;
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#else
+    const int threads = 1;
+#endif
+    SetSlots slots;
+    std::vector<uint32> rows(n_suffixes);                // the outputs stay untouched when the lengths do not add up
+    if (int e = set_suffix_sort_host(set, n_strings, n_suffixes, slots, rows.data(), threads)) return e;
+    std::copy(rows.begin(), rows.end(), suffixes_out);
+    if (string_ids_out) std::copy(slots.sid.begin(), slots.sid.end(), string_ids_out);
+    if (cum_lengths_out) for (uint32 s = 0; s < n_strings; ++s) cum_lengths_out[s] = uint32(slots.cum[s]);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_set_bwt_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint64_t n_suffixes, uint8_t* bwt_out,
+                                   uint32_t* dollar_rows_out, uint32_t* dollar_ids_out, uint32_t* suffixes_out, int32_t n_threads)
+{
+    if (int e = set_sufsort_args(set, n_strings, n_suffixes)) return e;
+    if (!bwt_out || !dollar_rows_out || !dollar_ids_out) return hipErrorInvalidValue;
+#if defined(_OPENMP)
+    const int threads = n_threads > 0 ? n_threads : omp_get_max_threads();
+#else
+    const int threads = 1;
+#endif
+    SetSlots slots;
+    std::vector<uint32> rows(n_suffixes);
+    if (int e = set_suffix_sort_host(set, n_strings, n_suffixes, slots, rows.data(), threads)) return e;
+    const uint32 be = set->big_endian ? 1u : 0u;
+    uint64 n_dollars = 0;
+    for (uint64 row = 0; row < n_suffixes; ++row)
+    {
+        const uint32 g = rows[row], s = slots.sid[g];
+        const uint64 p = g - (s ? slots.cum[s - 1] : 0u);
+        bwt_out[row] = p ? uint8(text_symbol(set->words, be, set->begin[s] + p - 1u)) : uint8(255u);
+        if (p == 0u) { dollar_rows_out[n_dollars] = uint32(row); dollar_ids_out[n_dollars] = s; ++n_dollars; }
+        if (suffixes_out) { suffixes_out[2u * row] = uint32(p); suffixes_out[2u * row + 1u] = s; }
+    }
+    return hipSuccess;
+}

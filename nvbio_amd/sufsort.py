@@ -96,3 +96,70 @@ def build_fm_index(text, sa_int=16, keep_sa=False):
     if keep_sa:
         return fmi, sa.to(torch.int64) & 0xFFFFFFFF
     return fmi
+
+
+# ---- string sets (nvbio_hip_set_suffix_sort / nvbio_hip_set_bwt): the suffixes of every string of a set, the empty ones included ----
+
+def _string_set(string_set, what):
+    """-> (PackedStringSet, n_strings, n_suffixes) of a 2-bit PackedStringSet or a list of uint8 symbol arrays (packed first)"""
+    from .strings import PackedStringSet
+    if not isinstance(string_set, PackedStringSet):
+        strings = [torch.as_tensor(t).to(torch.uint8).reshape(-1) for t in string_set]
+        if not strings:
+            raise ValueError(what + ": the set must hold at least one string")
+        dev = next((t.device for t in strings if t.is_cuda), torch.device("cuda"))
+        length = torch.tensor([t.numel() for t in strings], dtype=torch.int64)
+        begin = torch.cumsum(length, 0) - length
+        words = pack_symbols(torch.cat(strings).to(dev), 2, True, pad_words=1)
+        string_set = PackedStringSet(words, 2, True, begin.to(dev), length.to(torch.int32).to(dev))
+    n_strings = len(string_set)
+    if n_strings == 0:
+        raise ValueError(what + ": the set must hold at least one string")
+    if string_set.bits != 2:
+        raise ValueError(what + ": only 2-bit string sets are supported, this one has %d bits a symbol" % string_set.bits)
+    if string_set.length is not None:
+        n_suffixes = int((string_set.length.to(torch.int64) & 0xFFFFFFFF).sum()) + n_strings
+    else:
+        n_suffixes = n_strings * (string_set.fixed_length + 1)
+    if n_suffixes > MAX_LENGTH:
+        raise ValueError(what + ": the set has %d slots (symbols + strings), more than 2^32 - 2" % n_suffixes)
+    return string_set, n_strings, n_suffixes
+
+
+def set_suffix_sort(string_set):
+    """The suffixes of all the strings of a set, sorted: -> (suffixes, string_ids, cum_lengths), device int32 tensors holding uint32
+    values.  String s contributes the len[s] + 1 slots (s, p), 0 <= p <= len[s] (the empty suffix included); slot (s, p) has the global
+    index cum_lengths[s - 1] + p, cum_lengths = the inclusive sums of len + 1.  suffixes[row] = the global index on that row, in the
+    order of the symbols with a proper prefix first and equal suffixes by string id; string_ids[g] = the string of global index g.
+    `string_set`: a PackedStringSet with bits == 2, or a list of uint8 symbol arrays."""
+    ss, n_strings, n = _string_set(string_set, "set_suffix_sort")
+    L = lib()
+    dev = ss.words.device
+    suffixes = torch.empty(n, dtype=torch.int32, device=dev)
+    string_ids = torch.empty(n, dtype=torch.int32, device=dev)
+    cum = torch.empty(n_strings, dtype=torch.int32, device=dev)
+    tb = int(L.nvbio_hip_set_suffix_sort_temp_bytes(n, n_strings))
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    s = ss.struct()
+    check(L.nvbio_hip_set_suffix_sort(C.byref(s), n_strings, n, _vp(suffixes), _vp(string_ids), _vp(cum), _vp(temp), tb, current_stream_ptr()),
+          "nvbio_hip_set_suffix_sort")
+    return suffixes, string_ids, cum
+
+
+def set_bwt(string_set, keep_suffixes=False):
+    """The BWT of a string set: -> (bwt, dollar_rows, dollar_ids, suffixes).  bwt: uint8 [n_suffixes], the symbol before the suffix on
+    each row, 255 where the suffix is a whole string; dollar_rows: those rows, ascending, and dollar_ids: the string each starts (int32
+    tensors holding uint32 values); suffixes: int32 [n_suffixes, 2], the (position, string) of every row (None unless keep_suffixes)."""
+    ss, n_strings, n = _string_set(string_set, "set_bwt")
+    L = lib()
+    dev = ss.words.device
+    out = torch.empty(n, dtype=torch.uint8, device=dev)
+    rows = torch.empty(n_strings, dtype=torch.int32, device=dev)
+    ids = torch.empty(n_strings, dtype=torch.int32, device=dev)
+    pairs = torch.empty((n, 2), dtype=torch.int32, device=dev) if keep_suffixes else None
+    tb = int(L.nvbio_hip_set_bwt_temp_bytes(n, n_strings))
+    temp = torch.empty(tb, dtype=torch.uint8, device=dev)
+    s = ss.struct()
+    check(L.nvbio_hip_set_bwt(C.byref(s), n_strings, n, _vp(out), _vp(rows), _vp(ids), _vp(pairs), _vp(temp), tb, current_stream_ptr()),
+          "nvbio_hip_set_bwt")
+    return out, rows, ids, pairs
