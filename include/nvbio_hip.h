@@ -1204,7 +1204,8 @@ const char* nvbio_hip_last_kernel_cell(void);    /* the cell of a "pair" launch:
 const char* nvbio_hip_last_kernel_frame(void);   /* the frame of a "pair" launch's cell: "column" (no gap subtract on the horizontal step) or "row", else "" */
 const char* nvbio_hip_last_kernel_row(void);     /* the row of a "pair" launch around its cells: "fold2" (the sink folded once per two rows: the "column" frame unless NVBIO_HIP_PAIR_ROW is 1) or "plain", else "" */
 const char* nvbio_hip_last_kernel_const(void);   /* where a "pair" launch's cell keeps its key constants: "literal" (in the instructions: the "fold2" row unless NVBIO_HIP_PAIR_CONST is 1 or |gap_ext| > 3), "vector" (no launch of the library's) or "scalar", else "" */
-const char* nvbio_hip_last_kernel_sub(void);     /* where a "pair" launch's cell takes its substitution words from: "lds" (one LDS read per cell: the "literal" form unless NVBIO_HIP_PAIR_SUB is 1) or "perm" (a v_perm_b32 lookup in two table words per row), else "" */
+const char* nvbio_hip_last_kernel_sub(void);     /* where a "pair" launch's cell takes its substitution words from: "lds" (read from an LDS table, nvbio_hip_last_kernel_subread() says how many cells to a read: the "literal" form unless NVBIO_HIP_PAIR_SUB is 1) or "perm" (a v_perm_b32 lookup in two table words per row), else "" */
+const char* nvbio_hip_last_kernel_subread(void); /* the cells one LDS read of an "lds" launch serves: "pair" (two, a ds_read_b64 from a table of pairs: the default) or "single" (NVBIO_HIP_PAIR_SUB is 2), else "" */
 const char* nvbio_hip_last_kernel_fetch(void);   /* how a "pair" launch read its strings: "stream" (32-bit cursors, only new words loaded) or "generic", else "" */
 
 #ifdef __cplusplus

@@ -40,7 +40,7 @@ SYMBOLS = [
     "nvbio_hip_stream_synchronize", "nvbio_hip_stream_query", "nvbio_hip_host_malloc", "nvbio_hip_host_free", "nvbio_hip_stream_create", "nvbio_hip_stream_destroy",
     "nvbio_hip_comm_available", "nvbio_hip_device_count", "nvbio_hip_set_device", "nvbio_hip_get_device", "nvbio_hip_comm_unique_id", "nvbio_hip_comm_init_rank",
     "nvbio_hip_comm_init_all", "nvbio_hip_comm_destroy", "nvbio_hip_comm_rank", "nvbio_hip_gather_records", "nvbio_hip_comm_abort", "nvbio_hip_comm_set_transport",
-    "nvbio_hip_abi_version", "nvbio_hip_arch", "nvbio_hip_last_kernel", "nvbio_hip_last_kernel_detail", "nvbio_hip_last_kernel_cell", "nvbio_hip_last_kernel_frame", "nvbio_hip_last_kernel_row", "nvbio_hip_last_kernel_const", "nvbio_hip_last_kernel_sub", "nvbio_hip_last_kernel_fetch", "nvbio_hip_set_test_switch", "nvbio_hip_get_test_switch", "nvbio_hip_test_switch_name",
+    "nvbio_hip_abi_version", "nvbio_hip_arch", "nvbio_hip_last_kernel", "nvbio_hip_last_kernel_detail", "nvbio_hip_last_kernel_cell", "nvbio_hip_last_kernel_frame", "nvbio_hip_last_kernel_row", "nvbio_hip_last_kernel_const", "nvbio_hip_last_kernel_sub", "nvbio_hip_last_kernel_subread", "nvbio_hip_last_kernel_fetch", "nvbio_hip_set_test_switch", "nvbio_hip_get_test_switch", "nvbio_hip_test_switch_name",
 ]
 
 
@@ -275,6 +275,7 @@ def lib():
         L.nvbio_hip_last_kernel_row.restype = C.c_char_p
         L.nvbio_hip_last_kernel_const.restype = C.c_char_p
         L.nvbio_hip_last_kernel_sub.restype = C.c_char_p
+        L.nvbio_hip_last_kernel_subread.restype = C.c_char_p
         _lib = L
     return _lib
 

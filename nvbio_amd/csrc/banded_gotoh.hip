@@ -156,13 +156,14 @@ static bool pair_stream_admitted(const GotohParams& p)
 // ROW: PF_ROW2 for the column frame's cell (its sink folded once per two rows), 0 for the row as it was, which the row-frame cells
 // keep and NVBIO_HIP_PAIR_ROW = 1 asks for.  nvbio_hip_last_kernel_row() says which one ran.  With PF_ROW2, ROW also carries the
 // constants' placement (launch_pair), which nvbio_hip_last_kernel_const() reports, and where the substitution words come from
-// (nvbio_hip_last_kernel_sub()).
+// (nvbio_hip_last_kernel_sub(), and nvbio_hip_last_kernel_subread() for the cells one LDS read serves).
 template <typename CELL, int ROW>
 static hipError_t launch_pair_row(const GotohParams& p, hipStream_t s)
 {
     g_last_pair.row = (ROW & PF_ROW2) ? "fold2" : "plain";
     g_last_pair.consts = (ROW & PF_CONST2) ? "literal" : "scalar";
     g_last_pair.sub = (ROW & PF_SUBLDS) ? "lds" : "perm";
+    g_last_pair.subread = (ROW & PF_SUBLDS2) ? "pair" : (ROW & PF_SUBLDS) ? "single" : "";
     g_last_pair.fetch = "generic";
     if (!pair_stream_admitted(p)) return launch_band_pair<15, CELL, PF_SINK_VCC | ROW>(p, s);
     g_last_pair.fetch = "stream";
@@ -183,7 +184,15 @@ static hipError_t launch_pair(const GotohParams& p, hipStream_t s)
             // the cell's key constants K_j and the pair fold's 2 G as literals (banded_gotoh_pair.h, "Where the constants live"): one
             // instance per |G_e|.  NVBIO_HIP_PAIR_CONST = 1 keeps them in scalar registers, as a |G_e| above 3 does.  The literal
             // instances read their substitution words from LDS (PF_SUBLDS, "Where the substitution comes from");
-            // NVBIO_HIP_PAIR_SUB = 1 keeps the v_perm_b32 lookup, which every other instance has
+            // NVBIO_HIP_PAIR_SUB = 1 keeps the v_perm_b32 lookup, which every other instance has.  A read serves two cells
+            // (PF_SUBLDS2, "Two cells per read"); NVBIO_HIP_PAIR_SUB = 2 keeps one read per cell
+            if (test_switch(SW_PAIR_CONST) != 1 && test_switch(SW_PAIR_SUB) != 1 && test_switch(SW_PAIR_SUB) != 2)
+                switch (p.gap_ext) {
+                case  0: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_SUBLDS | PF_SUBLDS2>(p, s);
+                case -1: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_SUBLDS | PF_SUBLDS2 | PF_GE1>(p, s);
+                case -2: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_SUBLDS | PF_SUBLDS2 | PF_GE2>(p, s);
+                case -3: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_SUBLDS | PF_SUBLDS2 | PF_GE3>(p, s);
+                }
             if (test_switch(SW_PAIR_CONST) != 1 && test_switch(SW_PAIR_SUB) != 1)
                 switch (p.gap_ext) {
                 case  0: return launch_pair_row<CELL, PF_ROW2 | PF_CONST2 | PF_SUBLDS>(p, s);
@@ -775,4 +784,5 @@ NVB_API const char* nvbio_hip_last_kernel_frame(void)  { return pair_fact(nvb::g
 NVB_API const char* nvbio_hip_last_kernel_row(void)    { return pair_fact(nvb::g_last_pair.row); }
 NVB_API const char* nvbio_hip_last_kernel_const(void)  { return pair_fact(nvb::g_last_pair.consts); }
 NVB_API const char* nvbio_hip_last_kernel_sub(void)    { return pair_fact(nvb::g_last_pair.sub); }
+NVB_API const char* nvbio_hip_last_kernel_subread(void) { return pair_fact(nvb::g_last_pair.subread); }
 NVB_API const char* nvbio_hip_last_kernel_cell(void)   { return pair_fact(nvb::g_last_pair.cell); }

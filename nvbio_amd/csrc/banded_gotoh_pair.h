@@ -135,6 +135,32 @@
 //         loads; the compiler writes a counted s_waitcnt lgkmcnt before each cell block.
 //     The row has 1 + 2 + 15 simple ops where the lookup has 7 simple and 15 slow ones and two reads; it is 4 to 5 % faster
 //     (profiles/banded_pair/README.md).  NVBIO_HIP_PAIR_SUB = 1 keeps the lookup.
+//
+// Two cells per read.  PF_SUBLDS2 (with PF_SUBLDS) reads the words of two neighbouring columns with one ds_read_b64: eight address xors
+// and eight reads per row where PF_SUBLDS has fifteen of each.  The cells (col0, cell2, tail2) are the same instructions on the same
+// words, so every bound above holds unchanged.
+//   * the table s_sub2: 1 024 entries of 8 bytes (8 KB a block; s_sub is not allocated).  Entry
+//         index = d_A | c0_A << 2 | c0_B << 4 | d_B << 6 | N_A << 8 | N_B << 9
+//     holds {0, sub(c0_B, N_B), 0, sub(c0_A, N_A)} and the same for c1 = c0 ^ d: c0 = (nibble & 3) ^ t0 is the first column's code,
+//     d = t0 ^ t1 the xor of the two columns' text symbols (it depends on the columns alone, which is why the second field holds d and
+//     not c1: the row's part stays at one byte), N = nibble >= 4; sub is the match byte where the code is 0 and N is clear -- the bytes
+//     s_sub and s_tab give.  An entry's bank pair is index mod 32 = d_A, c0_A and the low bit of c0_B: the 256 entries A/C/G/T codes
+//     reach lie 8 to a bank pair, as evenly as any layout has them.
+//   * the row byte n_A & 3 | (n_B & 3) << 2 | N_A << 6 | N_B << 7 and the column pair byte d_A | t0_A << 2 | t0_B << 4 | d_B << 6 are
+//     kept as byte offsets, times 32 and times 8: the fields are ordered so that each is one contiguous byte and a row takes either
+//     with one SDWA shift.  A 16-row block builds four registers of row bytes (sub2_row_words) and four of pair bytes (sub2_col_words:
+//     T ^ (T << 2 | carried symbol) gives a job's sixteen d in one op); the symbol carried across the block seam is the second of the
+//     last pair formed, t0 ^ d of the ring's slot 12, where the prologue has put the pair (12, 13) of the band's first fourteen symbols.
+//   * the ring tc[] holds pair words: slot t & 15 the pair of text positions (t, t + 1).  Row i forms the pair (i + 13, i + 14) from its
+//     entering symbol and reads column 0 alone, a ds_read_b32 of the first word of pair (i, i + 1), and the pairs (i + 1, i + 2), ...,
+//     (i + 13, i + 14) for columns 1 ... 14, which is how cell2 and tail2 take their columns.  A pair is formed in the row that first
+//     reads it, read as a pair by seven rows and once more by column 0: fourteen live, the ring stays 16.
+//   * the reads are plain loads, the compiler writes the waits.  Each pair is read one cell2 ahead of the cell that takes it: with the
+//     landing registers two and two, the kernel has 95 VGPRs and no scratch, five waves.  The cells read the landing registers without
+//     rewriting them (a half of a 64-bit pair rewritten in place costs a v_mov_b32), and the kernel's epilogue works the job numbers out
+//     again from the lane's where the other forms keep them across the block loop.
+//   tests/test_pair_sub2_table.py holds the table, the words and the ring's schedule in numpy.  NVBIO_HIP_PAIR_SUB = 2 keeps one read
+//   per cell.  profiles/banded_pair/README.md has the probe's ceiling (sub-xor8), the form's figures and the counters.
 #pragma once
 #include "banded_gotoh_impl.h"
 
@@ -168,14 +194,20 @@ enum PairForm : int {
     // the substitution words read from LDS, one ds_read_b32 per cell, in place of the v_perm_b32 lookup (the header comment, "Where the
     // substitution comes from"); with PF_FOLD2 | PF_CONST2 only
     PF_SUBLDS   = 262144,
-    PF_KO_PERM  = 524288                                                            // probe only: PF_CONST2's row, a v_xor_b32 for each v_perm_b32
+    PF_KO_PERM  = 524288,                                                           // probe only: PF_CONST2's row, a v_xor_b32 for each v_perm_b32
+    // PF_SUBLDS with two cells' words to a read, ds_read_b64 from a table of 1 024 pairs ("Two cells per read"); with PF_SUBLDS only
+    PF_SUBLDS2  = 1048576,
+    // probe only, on PF_SUBLDS's rows: eight address xors and eight two-word reads per row, the second word the table's next one (no
+    // results); one s_nop behind each run of address xors; PF_CONST2's pad in col0 and tail2 as well
+    PF_KO_XOR8  = 2097152, PF_PAD_XOR = 4194304, PF_PAD_EDGE = 8388608,
+    PF_AHEAD2   = 16777216                                                          // probe only: PF_SUBLDS2's reads two pairs ahead of the cells, not one
 };
 constexpr int pair_ge(int form)     { return (form / PF_GE1) & 3; }
 constexpr int pair_ge_bits(int ge)  { return ge * PF_GE1; }
 // the row the library launches for PD3 (banded_gotoh.hip: launch_pair; NVBIO_HIP_PAIR_ROW = 1 keeps the row without it).  With it the
 // library launches PF_CONST2 (NVBIO_HIP_PAIR_CONST = 1 keeps the scalars), one instance per |G_e| 0 ... 3 (a scheme with a larger
 // |G_e|, which only negative match scores admit, keeps the scalars too), and with PF_CONST2 it launches PF_SUBLDS
-// (NVBIO_HIP_PAIR_SUB = 1 keeps the lookup)
+// (NVBIO_HIP_PAIR_SUB = 1 keeps the lookup), two cells to a read (PF_SUBLDS2; NVBIO_HIP_PAIR_SUB = 2 keeps one read per cell)
 constexpr int PF_ROW2 = PF_FOLD2;
 // the streamed forms the library holds: every pattern width and byte order it streams.  X(form), or Y(A, form) with one more argument
 #define NVB_PAIR_STREAM_FORMS_(Y, A) \
@@ -184,16 +216,18 @@ constexpr int PF_ROW2 = PF_FOLD2;
 #define NVB_PAIR_APPLY_(X, F) X(F)
 #define NVB_PAIR_STREAM_FORMS(X) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_APPLY_, X)
 // every instance the library holds, as X(cell, form): the generic fetches and every streamed form, each for the three cells and PD3
-// with PF_ROW2, and for PD3 with PF_ROW2 | PF_CONST2 and each |G_e|, with the v_perm_b32 lookup and with PF_SUBLDS.  In three parts,
-// named for the three translation units that share their compile time (banded_gotoh_pair_b15.hip, banded_gotoh_pair_b15_lit.hip for
-// the lookup, banded_gotoh_pair_b15_sub.hip for PF_SUBLDS)
+// with PF_ROW2, and for PD3 with PF_ROW2 | PF_CONST2 and each |G_e|, with the v_perm_b32 lookup, with PF_SUBLDS and with PF_SUBLDS2.  In
+// four parts, named for the four translation units that share their compile time (banded_gotoh_pair_b15.hip,
+// banded_gotoh_pair_b15_lit.hip for the lookup, banded_gotoh_pair_b15_sub.hip for PF_SUBLDS, banded_gotoh_pair_b15_sub2.hip for PF_SUBLDS2)
 #define NVB_PAIR_CELLS_(X, F) X(P16, (F)) X(PM3, (F)) X(PD3, (F)) X(PD3, (F) | PF_ROW2)
 #define NVB_PAIR_GES_(X, F)   X(PD3, (F) | PF_ROW2 | PF_CONST2) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE1) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE2) X(PD3, (F) | PF_ROW2 | PF_CONST2 | PF_GE3)
 #define NVB_PAIR_INSTANCES_B15(X)     NVB_PAIR_CELLS_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_CELLS_, X)
 #define NVB_PAIR_INSTANCES_B15_LIT(X) NVB_PAIR_GES_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_GES_, X)
 #define NVB_PAIR_SUBS_(X, F)  NVB_PAIR_GES_(X, (F) | PF_SUBLDS)
 #define NVB_PAIR_INSTANCES_B15_SUB(X) NVB_PAIR_SUBS_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_SUBS_, X)
-#define NVB_PAIR_INSTANCES(X)         NVB_PAIR_INSTANCES_B15(X) NVB_PAIR_INSTANCES_B15_LIT(X) NVB_PAIR_INSTANCES_B15_SUB(X)
+#define NVB_PAIR_SUB2S_(X, F) NVB_PAIR_GES_(X, (F) | PF_SUBLDS | PF_SUBLDS2)
+#define NVB_PAIR_INSTANCES_B15_SUB2(X) NVB_PAIR_SUB2S_(X, PF_SINK_VCC) NVB_PAIR_STREAM_FORMS_(NVB_PAIR_SUB2S_, X)
+#define NVB_PAIR_INSTANCES(X)         NVB_PAIR_INSTANCES_B15(X) NVB_PAIR_INSTANCES_B15_LIT(X) NVB_PAIR_INSTANCES_B15_SUB(X) NVB_PAIR_INSTANCES_B15_SUB2(X)
 
 // PF_SUBLDS's table index (the header comment, "Where the substitution comes from"): with c = nibble ^ symbol of job A and of job B,
 //   index = c_A & 3 | c_B << 2 | (c_A >> 2) << 6,
@@ -216,6 +250,50 @@ __device__ __forceinline__ void sub_row_words(const uint64_t PA, const uint64_t 
         ro[h] = sub_bfi(0x03030303u, a >> 4, sub_bfi(0x3C3C3C3Cu, b >> 2, a));
     }
     RE = re[0] | uint64_t(re[1]) << 32; RO = ro[0] | uint64_t(ro[1]) << 32;
+}
+
+// PF_SUBLDS2's table index (the header comment, "Two cells per read"): entry
+//   index = d_A | c0_A << 2 | c0_B << 4 | d_B << 6 | N_A << 8 | N_B << 9
+// holds the words of the cells with codes c0 and c0 ^ d.  It is the xor of a row byte shifted up by 2 and a column pair byte:
+//   row byte    = n_A & 3 | (n_B & 3) << 2 | N_A << 6 | N_B << 7      (n: the row's nibble, N = n >= 4)
+//   column byte = d_A | t0_A << 2 | t0_B << 4 | d_B << 6              (t0: the pair's first text symbol, d = t0 ^ t1)
+// Both are kept as byte offsets of the 8-byte entries: the row byte times 32, the column byte times 8.
+__host__ __device__ constexpr uint32_t sub2_index(uint32_t c0a, uint32_t c0b, uint32_t da, uint32_t db, uint32_t na, uint32_t nb)
+{
+    return da | (c0a << 2) | (c0b << 4) | (db << 6) | (na << 8) | (nb << 9);
+}
+__host__ __device__ constexpr uint32_t sub2_row_byte(uint32_t nib_a, uint32_t nib_b) { return (nib_a & 3u) | ((nib_b & 3u) << 2) | (nib_a >= 4u ? 64u : 0u) | (nib_b >= 4u ? 128u : 0u); }
+__host__ __device__ constexpr uint32_t sub2_col_byte(uint32_t t0a, uint32_t t0b, uint32_t t1a, uint32_t t1b) { return (t0a ^ t1a) | (t0a << 2) | (t0b << 4) | ((t0b ^ t1b) << 6); }
+// entry `index`, word h (0: the pair's first cell, 1: its second): {0, sub(c_B, N_B), 0, sub(c_A, N_A)}, the match byte sm where the code
+// is 0 and N is clear, the mismatch byte sx elsewhere
+__host__ __device__ constexpr uint32_t sub2_word(uint32_t index, uint32_t h, uint32_t sm, uint32_t sx)
+{
+    const uint32_t ca = ((index >> 2) & 3u) ^ (h ? index & 3u : 0u), cb = ((index >> 4) & 3u) ^ (h ? (index >> 6) & 3u : 0u);
+    return ((ca == 0u && !(index & 256u)) ? sm : sx) | (((cb == 0u && !(index & 512u)) ? sm : sx) << 16);
+}
+// a 16-row block's row bytes: byte k of RE is row 2 k's, byte k of RO row 2 k + 1's, as sub_row_words has them
+__device__ __forceinline__ void sub2_row_words(const uint64_t PA, const uint64_t PB, uint64_t& RE, uint64_t& RO)
+{
+    uint32_t re[2], ro[2];
+    #pragma unroll
+    for (int h = 0; h < 2; ++h)
+    {
+        const uint32_t a = uint32_t(PA >> (32 * h)), b = uint32_t(PB >> (32 * h));
+        const uint32_t na = (a | (a >> 1)) & 0x44444444u, nb = (b | (b >> 1)) & 0x44444444u;     // N at bit 2 of every nibble
+        re[h] = (a & 0x03030303u)        | ((b << 2) & 0x0C0C0C0Cu) | ((na << 4) & 0x40404040u) | ((nb << 5) & 0x80808080u);
+        ro[h] = ((a >> 4) & 0x03030303u) | ((b >> 2) & 0x0C0C0C0Cu) | (na & 0x40404040u)        | ((nb << 1) & 0x80808080u);
+    }
+    RE = re[0] | uint64_t(re[1]) << 32; RO = ro[0] | uint64_t(ro[1]) << 32;
+}
+// a 16-row block's entering column pair bytes: byte m of CW[q] is row 4 m + q's, the pair of the symbol that entered a row before
+// (TA / TB's symbol r - 1; prev_a / prev_b before symbol 0) and the row's own.  T ^ T' gives every d of a job in one op
+__device__ __forceinline__ void sub2_col_words(const uint32_t TA, const uint32_t TB, const uint32_t prev_a, const uint32_t prev_b, uint32_t (&CW)[4])
+{
+    const uint32_t PA = (TA << 2) | prev_a, PB = (TB << 2) | prev_b, DA = TA ^ PA, DB = TB ^ PB;
+    const uint32_t ue = sub_bfi(0x33333333u, DA, PA << 2), uo = sub_bfi(0x33333333u, DA >> 2, PA);       // nibble k: d_A | t0_A << 2 of row 2 k / 2 k + 1
+    const uint32_t ve = sub_bfi(0x33333333u, PB, DB << 2), vo = sub_bfi(0x33333333u, PB >> 2, DB);       // nibble k: t0_B | d_B << 2
+    CW[0] = sub_bfi(0x0F0F0F0Fu, ue, ve << 4); CW[2] = sub_bfi(0x0F0F0F0Fu, ue >> 4, ve);
+    CW[1] = sub_bfi(0x0F0F0F0Fu, uo, vo << 4); CW[3] = sub_bfi(0x0F0F0F0Fu, uo >> 4, vo);
 }
 
 // what both cells share: the replicated constants, the substitution lookup and the sink
@@ -469,12 +547,13 @@ struct PD3 : PairOps {
 #define NVB_PD3_PERM2 "v_perm_b32 %[d0], %[thi], %[tlo], %[g0]\n\t" "v_perm_b32 %[d1], %[thi], %[tlo], %[g1]\n\t"
 #define NVB_PD3_XOR1  "v_xor_b32 %[d], %[tlo], %[g0]\n\t"
 #define NVB_PD3_XOR2  "v_xor_b32 %[d0], %[tlo], %[g0]\n\t" "v_xor_b32 %[d1], %[tlo], %[g1]\n\t"
-#define NVB_PD3_COL0(L) L \
+#define NVB_PD3_COL0_(L, P, Q) L \
             "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
-            "v_add_u32 %[d], %[s0], %[d]\n\t" \
+            "v_add_u32 %[d], %[s0], %[d]\n\t" P \
             "v_pk_max_u16 %[h], %[f0], %[d]\n\t" \
             "v_subrev_u32 %[s0], %[dd], %[h]\n\t" \
-            "v_add_u32 %[rk], %[k0], %[h]"
+            "v_add_u32 %[rk], %[k0], %[h]" Q
+#define NVB_PD3_COL0(L) NVB_PD3_COL0_(L, "", "")
 #define NVB_PD3_COL0_OUT [f0] "=&v"(F0), [d] "=&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
 #define NVB_PD3_COL0_IN  [g0] "v"(g0), [tlo] "v"(tlo), [thi] "v"(thi), [f1] "v"(F1), [s1] "v"(S1), [z0] "s"(Z0)
     template <int FORM>
@@ -482,7 +561,9 @@ struct PD3 : PairOps {
                                                 const uint32_t g0, const uint32_t D, const uint32_t tlo, const uint32_t thi, const uint32_t Z0, const uint32_t K0)
     {
         uint32_t d = g0, h;
-        if constexpr ((FORM & PF_SUBLDS) != 0)      asm(NVB_PD3_COL0("") : [f0] "=&v"(F0), [d] "+&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
+        if constexpr ((FORM & PF_PAD_EDGE) != 0)    asm(NVB_PD3_COL0_("", "s_nop 0\n\t", "\n\ts_nop 0") : [f0] "=&v"(F0), [d] "+&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
+                                                                         : [f1] "v"(F1), [s1] "v"(S1), [z0] "s"(Z0), [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
+        else if constexpr ((FORM & PF_SUBLDS) != 0) asm(NVB_PD3_COL0("") : [f0] "=&v"(F0), [d] "+&v"(d), [h] "=&v"(h), [s0] "+&v"(S0), [rk] "=&v"(rowkey)
                                                                          : [f1] "v"(F1), [s1] "v"(S1), [z0] "s"(Z0), [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
         else if constexpr ((FORM & PF_KO_PERM) != 0) asm(NVB_PD3_COL0(NVB_PD3_XOR1) : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
         else if constexpr ((FORM & PF_CONST2) != 0) asm(NVB_PD3_COL0(NVB_PD3_PERM1) : NVB_PD3_COL0_OUT : NVB_PD3_COL0_IN, [dd] "v"(D), [k0] "n"(klit<FORM>(0)));
@@ -492,11 +573,11 @@ struct PD3 : PairOps {
     // PM3::cell2 without E's subtracts: E'(J+1) = max(E'(J), S'(J)).  Ein: E'(i,J), read only (column 1's is S'(i,0), which stays live as
     // the next row's diagonal); E: E'(i,J+2).  Z0, Z1: Z(i,J), Z(i,J+1); K0, K1: K_J, K_(J+1); they and D are scalars, one to an instruction.
     // P: PF_CONST2's pad behind each group of simple ops, or nothing
-#define NVB_PD3_CELL2(L, P) L \
+#define NVB_PD3_CELL2_(L, P, W0, W1) L \
             "v_pk_maximum3_f16 %[f0], %[f1], %[s1], %[z0]\n\t" \
             "v_pk_maximum3_f16 %[f1], %[f2], %[s2], %[z1]\n\t" \
-            "v_add_u32 %[d0], %[s0], %[d0]\n\t" \
-            "v_add_u32 %[d1], %[s1], %[d1]\n\t" P \
+            "v_add_u32 %[d0], %[s0], " W0 "\n\t" \
+            "v_add_u32 %[d1], %[s1], " W1 "\n\t" P \
             "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t" \
             "v_subrev_u32 %[s0], %[dd], %[h]\n\t" \
             "v_add_u32 %[d0], %[k0], %[h]\n\t" P \
@@ -506,6 +587,9 @@ struct PD3 : PairOps {
             "v_add_u32 %[d1], %[k1], %[h]\n\t" P \
             "v_pk_max_u16 %[e], %[e], %[s1]\n\t" \
             "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+// (W0, W1: where the diagonals' words stand: in d0 / d1 themselves, or, for the two halves of PF_SUBLDS2's 64-bit reads, in g0 / g1,
+// which the cell only reads: a half of a register pair rewritten in place costs a v_mov_b32)
+#define NVB_PD3_CELL2(L, P) NVB_PD3_CELL2_(L, P, "%[d0]", "%[d1]")
 #define NVB_PD3_CELL2_OUT [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
 #define NVB_PD3_CELL2_IN  [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1)
     // J: the first of the two columns (PF_CONST2's literals are its and the next one's)
@@ -515,7 +599,11 @@ struct PD3 : PairOps {
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
         uint32_t d0 = g0, d1 = g1, h;
-        if constexpr ((FORM & PF_SUBLDS) != 0)
+        if constexpr ((FORM & PF_SUBLDS2) != 0)
+            asm(NVB_PD3_CELL2_("", "s_nop 0\n\t", "%[g0]", "%[g1]")
+                : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
+                : [g0] "v"(g0), [g1] "v"(g1), [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_SUBLDS) != 0)
             asm(NVB_PD3_CELL2("", "s_nop 0\n\t")
                 : [f0] "=&v"(F0), [f1] "+&v"(F1), [d0] "+&v"(d0), [d1] "+&v"(d1), [h] "=&v"(h), [s0] "+&v"(S0), [s1] "+&v"(S1), [e] "=&v"(E), [rk] "+&v"(rowkey)
                 : [f2] "v"(F2), [s2] "v"(S2), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
@@ -526,18 +614,19 @@ struct PD3 : PairOps {
 
     // PM3::tail2 in the column frame: the cell J next to the band's edge (F' = max(S'(i-1,J+1), Z(i,J))) and the last column J + 1
     // (h = max3(E', diagonal, Z(i,J+1)))
-#define NVB_PD3_TAIL2(L) L \
+#define NVB_PD3_TAIL2_(L, P, W0, W1) L \
             "v_pk_max_u16 %[f0], %[s1], %[z0]\n\t" \
-            "v_add_u32 %[d0], %[s0], %[d0]\n\t" \
-            "v_add_u32 %[d1], %[s1], %[d1]\n\t" \
+            "v_add_u32 %[d0], %[s0], " W0 "\n\t" \
+            "v_add_u32 %[d1], %[s1], " W1 "\n\t" P \
             "v_pk_maximum3_f16 %[h], %[f0], %[d0], %[ei]\n\t" \
             "v_subrev_u32 %[s0], %[dd], %[h]\n\t" \
-            "v_add_u32 %[d0], %[k0], %[h]\n\t" \
+            "v_add_u32 %[d0], %[k0], %[h]\n\t" P \
             "v_pk_max_u16 %[e], %[ei], %[s0]\n\t" \
             "v_pk_maximum3_f16 %[h], %[e], %[d1], %[z1]\n\t" \
             "v_subrev_u32 %[s1], %[dd], %[h]\n\t" \
-            "v_add_u32 %[d1], %[k1], %[h]\n\t" \
+            "v_add_u32 %[d1], %[k1], %[h]\n\t" P \
             "v_pk_maximum3_f16 %[rk], %[rk], %[d0], %[d1]"
+#define NVB_PD3_TAIL2(L) NVB_PD3_TAIL2_(L, "", "%[d0]", "%[d1]")
 #define NVB_PD3_TAIL2_OUT [f0] "=&v"(F0), [d0] "=&v"(d0), [d1] "=&v"(d1), [h] "=&v"(h), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
 #define NVB_PD3_TAIL2_IN  [g0] "v"(g0), [g1] "v"(g1), [tlo] "v"(tlo), [thi] "v"(thi), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1)
     template <int FORM, int J>
@@ -546,7 +635,17 @@ struct PD3 : PairOps {
                                                  const uint32_t Z0, const uint32_t Z1, const uint32_t K0, const uint32_t K1)
     {
         uint32_t d0 = g0, d1 = g1, h, e;
-        if constexpr ((FORM & PF_SUBLDS) != 0)
+        if constexpr ((FORM & PF_SUBLDS2) != 0 && (FORM & PF_PAD_EDGE) != 0)
+            asm(NVB_PD3_TAIL2_("", "s_nop 0\n\t", "%[g0]", "%[g1]") : NVB_PD3_TAIL2_OUT
+                : [g0] "v"(g0), [g1] "v"(g1), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_SUBLDS2) != 0)
+            asm(NVB_PD3_TAIL2_("", "", "%[g0]", "%[g1]") : NVB_PD3_TAIL2_OUT
+                : [g0] "v"(g0), [g1] "v"(g1), [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_PAD_EDGE) != 0)
+            asm(NVB_PD3_TAIL2_("", "s_nop 0\n\t", "%[d0]", "%[d1]")
+                : [f0] "=&v"(F0), [d0] "+&v"(d0), [d1] "+&v"(d1), [h] "=&v"(h), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
+                : [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
+        else if constexpr ((FORM & PF_SUBLDS) != 0)
             asm(NVB_PD3_TAIL2("")
                 : [f0] "=&v"(F0), [d0] "+&v"(d0), [d1] "+&v"(d1), [h] "=&v"(h), [e] "=&v"(e), [s0] "+&v"(S0), [s1] "+&v"(S1), [rk] "+&v"(rowkey)
                 : [ei] "v"(Ein), [z0] "s"(Z0), [z1] "s"(Z1), [dd] "v"(D), [k0] "n"(klit<FORM>(J)), [k1] "n"(klit<FORM>(J + 1)));
@@ -586,6 +685,32 @@ struct PD3 : PairOps {
         static __device__ __forceinline__ void run(PairState<BAND>&, const ColumnFrame<BAND>&, const uint32_t Ein, uint32_t& E, uint32_t&, const uint32_t (&)[BAND]) { E = Ein; }
     };
 
+    // PF_SUBLDS2: pair k's read, the words of columns 2 k - 1 and 2 k of row R, and the cells with the reads sub2_ahead() pairs ahead of them
+    template <int FORM> static constexpr int sub2_ahead() { return (FORM & PF_AHEAD2) ? 2 : 1; }   // (two: the probe's; 96 VGPRs and one register spilled around the block loop)
+    template <int BAND, int R, int FORM>
+    static __device__ __forceinline__ void sub2_read(const PairState<BAND>& st, uint32_t (&w)[BAND], const uint32_t rw, const uint32_t* sub, const int k)
+    {
+        uint32_t a = rw ^ st.tc[(R + 2 * k - 1) & 15];
+        if constexpr ((FORM & PF_PAD_XOR) != 0) asm volatile("s_nop 0" : "+v"(a));
+        const uint2 t = *reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(sub) + a);
+        w[2 * k - 1] = t.x; w[2 * k] = t.y;
+    }
+    template <int BAND, int R, int FORM, int K, int END>
+    struct Sub2Cells {
+        static __device__ __forceinline__ void run(PairState<BAND>& st, const ColumnFrame<BAND>& fr, const uint32_t Ein, uint32_t& E, uint32_t& rowkey, uint32_t (&w)[BAND],
+                                                   const uint32_t rw, const uint32_t* sub)
+        {
+            uint32_t En;
+            if constexpr (K + sub2_ahead<FORM>() <= (BAND - 1) / 2) sub2_read<BAND, R, FORM>(st, w, rw, sub, K + sub2_ahead<FORM>());
+            SubCells<BAND, R, FORM, 2 * K - 1, 2 * K + 1>::run(st, fr, Ein, En, rowkey, w);
+            Sub2Cells<BAND, R, FORM, K + 1, END>::run(st, fr, En, E, rowkey, w, rw, sub);
+        }
+    };
+    template <int BAND, int R, int FORM, int END>
+    struct Sub2Cells<BAND, R, FORM, END, END> {
+        static __device__ __forceinline__ void run(PairState<BAND>&, const ColumnFrame<BAND>&, const uint32_t Ein, uint32_t& E, uint32_t&, uint32_t (&)[BAND], uint32_t, const uint32_t*) { E = Ein; }
+    };
+
     // the wave's frame before row 0: slot s of the ring holds Z(0, s) = BIAS' + G (2 + s) for the columns row 0's prologue leaves alone and
     // 16 G less for the two it advances (and for slot 15, which row 1 advances before its first use)
     template <int BAND>
@@ -610,7 +735,42 @@ struct PD3 : PairOps {
         fr.z[(2 * R + BAND - 2) & 15] += fr.step;
         fr.z[(2 * R + BAND - 1) & 15] += fr.step;
         uint32_t rowkey, E;
-        if constexpr ((FORM & PF_SUBLDS) != 0)
+        if constexpr ((FORM & PF_SUBLDS2) != 0)
+        {
+            // g_new: the entering pair's column word, (i + 13, i + 14); tlo: the row word; sub: the block's table of pairs.  Column 0 reads
+            // the first word of its pair (i, i + 1), columns 1 ... 14 go two to a read, pair k = 1 ... 7 for columns 2 k - 1 and 2 k.  The
+            // reads run sub2_ahead() pairs ahead of the cells, one: a cell's pair is read while the cell before it runs (Sub2Cells)
+            st.tc[(R + BAND - 2) & 15] = g_new;
+            uint32_t w[BAND];
+            uint32_t a0 = tlo ^ st.tc[R & 15];
+            if constexpr ((FORM & PF_PAD_XOR) != 0) asm volatile("s_nop 0" : "+v"(a0));
+            w[0] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + a0);
+            #pragma unroll
+            for (int k = 1; k <= sub2_ahead<FORM>(); ++k) sub2_read<BAND, R, FORM>(st, w, tlo, sub, k);
+            col0<FORM>(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, w[0], fr.D, 0u, 0u, fr.z[(2 * R) & 15], fr.k[0]);
+            Sub2Cells<BAND, R, FORM, 1, (BAND - 1) / 2>::run(st, fr, st.S[0], E, rowkey, w, tlo, sub);
+            tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, w[BAND - 2], w[BAND - 1], fr.D, 0u, 0u,
+                                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        }
+        else if constexpr ((FORM & PF_KO_XOR8) != 0)
+        {
+            // the probe's ceiling for the form above: PF_SUBLDS's row and table with a read of two adjacent words for every other column,
+            // eight xors and eight reads; the second word is whatever follows the first in the table (the kernel pads it by one)
+            struct alignas(4) W2 { uint32_t x, y; };
+            constexpr int HEAD = 8, SPLIT = 5;
+            st.tc[(R + BAND - 1) & 15] = g_new;
+            uint32_t w[BAND], Em;
+            #pragma unroll
+            for (int j = 0; j < HEAD; j += 2) { const W2 t = *reinterpret_cast<const W2*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15])); w[j] = t.x; if (j + 1 < BAND) w[j + 1] = t.y; }
+            col0<FORM>(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, w[0], fr.D, 0u, 0u, fr.z[(2 * R) & 15], fr.k[0]);
+            SubCells<BAND, R, FORM, 1, SPLIT>::run(st, fr, st.S[0], Em, rowkey, w);
+            #pragma unroll
+            for (int j = HEAD; j < BAND; j += 2) { const W2 t = *reinterpret_cast<const W2*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15])); w[j] = t.x; if (j + 1 < BAND) w[j + 1] = t.y; }
+            SubCells<BAND, R, FORM, SPLIT, BAND - 2>::run(st, fr, Em, E, rowkey, w);
+            tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, w[BAND - 2], w[BAND - 1], fr.D, 0u, 0u,
+                                  fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
+        }
+        else if constexpr ((FORM & PF_SUBLDS) != 0)
         {
             // g_new: the entering column word; tlo: the row word; sub: the block's table.  The reads go out in two batches, each in the
             // order the cells take its words, so the counted waits fall before each cell block: columns 0 ... 7 at the row's head, the
@@ -618,12 +778,36 @@ struct PD3 : PairOps {
             constexpr int HEAD = 8, SPLIT = 5;
             st.tc[(R + BAND - 1) & 15] = g_new;
             uint32_t w[BAND], Em;
-            #pragma unroll
-            for (int j = 0; j < HEAD; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15]));
+            if constexpr ((FORM & PF_PAD_XOR) != 0)                                    // the probe's pad behind each run of xors
+            {
+                uint32_t a[HEAD];
+                #pragma unroll
+                for (int j = 0; j < HEAD; ++j) a[j] = tlo ^ st.tc[(R + j) & 15];
+                asm volatile("s_nop 0" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]));
+                #pragma unroll
+                for (int j = 0; j < HEAD; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + a[j]);
+            }
+            else
+            {
+                #pragma unroll
+                for (int j = 0; j < HEAD; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15]));
+            }
             col0<FORM>(st.F[0], st.F[1], st.S[0], st.S[1], rowkey, w[0], fr.D, 0u, 0u, fr.z[(2 * R) & 15], fr.k[0]);
             SubCells<BAND, R, FORM, 1, SPLIT>::run(st, fr, st.S[0], Em, rowkey, w);
-            #pragma unroll
-            for (int j = HEAD; j < BAND; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15]));
+            if constexpr ((FORM & PF_PAD_XOR) != 0)
+            {
+                uint32_t a[BAND - HEAD];
+                #pragma unroll
+                for (int j = HEAD; j < BAND; ++j) a[j - HEAD] = tlo ^ st.tc[(R + j) & 15];
+                asm volatile("s_nop 0" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]));
+                #pragma unroll
+                for (int j = HEAD; j < BAND; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + a[j - HEAD]);
+            }
+            else
+            {
+                #pragma unroll
+                for (int j = HEAD; j < BAND; ++j) w[j] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(sub) + (tlo ^ st.tc[(R + j) & 15]));
+            }
             SubCells<BAND, R, FORM, SPLIT, BAND - 2>::run(st, fr, Em, E, rowkey, w);
             tail2<FORM, BAND - 2>(st.F[BAND - 2], st.S[BAND - 2], st.S[BAND - 1], E, rowkey, w[BAND - 2], w[BAND - 1], fr.D, 0u, 0u,
                                   fr.z[(2 * R + BAND - 2) & 15], fr.z[(2 * R + BAND - 1) & 15], fr.k[BAND - 2], fr.k[BAND - 1]);
@@ -662,19 +846,32 @@ struct PairRows {
     // (KT: the resident table of the probe's PF_KO_TABLE, otherwise unused)
     // fr: the column frame's scalars (CELL::COLUMN; the row-frame cells take D and G instead)
     // rk2: the even row's row key, which the column frame's row carries to the odd row (PF_FOLD2; unused otherwise)
+    // (NX: 2, or PF_SUBLDS2's 4)
+    template <int NX>
     static __device__ __forceinline__ void run(PairState<BAND>& st, ColumnFrame<BAND>& fr, const uint32_t i0, const uint32_t M, const uint32_t D, const uint32_t G,
-                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[2], const uint32_t* tab, const uint32_t (&KT)[2], uint32_t& rk2)
+                                               const uint64_t PA, const uint64_t PB, const uint32_t (&XT)[NX], const uint32_t* tab, const uint32_t (&KT)[2], uint32_t& rk2)
     {
         if ((FORM & PF_KO_BOUND) || i0 + R < M)
         {
-            if constexpr ((FORM & PF_SUBLDS) != 0)
+            if constexpr ((FORM & PF_SUBLDS2) != 0)
+            {
+                // PA / PB hold the block's row bytes of the even / the odd rows (sub2_row_words) and XT[q] the entering pair bytes of the
+                // rows 4 m + q (sub2_col_words): both leave here as byte offsets, the row byte times 32 and the pair byte times 8
+                constexpr int K = R >> 1, Q = R >> 2;
+                const uint32_t zw = uint32_t(((R & 1) ? PB : PA) >> (32 * (K >> 2))), xw = XT[R & 3];
+                uint32_t rw = (K & 3) == 0 ? (zw << 5) & 0x1FE0u : (zw >> ((8 * (K & 3) + 27) & 31)) & 0x1FE0u;
+                uint32_t cw = Q == 0 ? (xw << 3) & 0x7F8u : (xw >> ((8 * Q + 29) & 31)) & 0x7F8u;
+                asm("" : "+v"(rw)); asm("" : "+v"(cw));                               // whole words, as below
+                CELL::template row<BAND, R, FORM>(st, fr, i0 + R, cw, rw, 0u, rk2, tab);
+            }
+            else if constexpr ((FORM & PF_SUBLDS) != 0)
             {
                 // PA / PB hold the block's row words of the even / the odd rows, a byte each, and XT[0] / XT[1] the entering column
                 // words of the even / the odd rows, a nibble each (sub_row_words; the kernel's block loop): both leave here as byte offsets
                 constexpr int K = R >> 1;
                 const uint32_t zw = uint32_t(((R & 1) ? PB : PA) >> (32 * (K >> 2))), xw = XT[R & 1];
-                uint32_t rw = (K & 3) == 0 ? (zw << 2) & 0x3FCu : (zw >> (8 * (K & 3) - 2)) & 0x3FCu;
-                uint32_t cw = K == 0 ? (xw << 2) & 0x3Cu : (xw >> (4 * K - 2)) & 0x3Cu;
+                uint32_t rw = (K & 3) == 0 ? (zw << 2) & 0x3FCu : (zw >> ((8 * (K & 3) + 30) & 31)) & 0x3FCu;
+                uint32_t cw = K == 0 ? (xw << 2) & 0x3Cu : (xw >> ((4 * K + 30) & 31)) & 0x3Cu;
                 asm("" : "+v"(rw)); asm("" : "+v"(cw));                               // whole words: the cells' xors take no mask along (a three-source op, and a scalar)
                 CELL::template row<BAND, R, FORM>(st, fr, i0 + R, cw, rw, 0u, rk2, tab);
             }
@@ -695,7 +892,8 @@ struct PairRows {
     }
 };
 template <typename CELL, int BAND, int FORM, int END> struct PairRows<CELL, BAND, FORM, END, END> {
-    static __device__ __forceinline__ void run(PairState<BAND>&, ColumnFrame<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[2], const uint32_t*, const uint32_t (&)[2], uint32_t&) {}
+    template <int NX>
+    static __device__ __forceinline__ void run(PairState<BAND>&, ColumnFrame<BAND>&, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, const uint32_t (&)[NX], const uint32_t*, const uint32_t (&)[2], uint32_t&) {}
 };
 
 // Lane k of the launch takes jobs 2k and 2k + 1 (with an odd n the last lane computes its one job in both halves).  The host has
@@ -713,17 +911,27 @@ __global__ void __launch_bounds__(PAIR_LANES) __attribute__((amdgpu_waves_per_eu
 banded_gotoh_pair_kernel(const GotohParams p)
 {
     static_assert(BAND >= 3 && BAND <= 16, "the ring of 16");
-    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0, FOLD2 = (FORM & PF_FOLD2) != 0, SUBLDS = (FORM & PF_SUBLDS) != 0;
+    constexpr bool STREAM = (FORM & PF_STREAM) != 0, KEY = (FORM & PF_SINK_KEY) != 0, FOLD2 = (FORM & PF_FOLD2) != 0, SUBLDS = (FORM & PF_SUBLDS) != 0, SUBLDS2 = (FORM & PF_SUBLDS2) != 0;
     static_assert(!(FORM & (PF_SUBLDS | PF_KO_PERM)) || ((FORM & PF_FOLD2) && (FORM & PF_CONST2) == PF_CONST2), "the LDS words and the probe's xor row are forms of the library's row");
     static_assert(!SUBLDS || !(FORM & (PF_KO_TABLE | PF_KO_PERM)), "the LDS words have no lookup to knock out");
+    static_assert(!(FORM & (PF_SUBLDS2 | PF_KO_XOR8 | PF_PAD_XOR | PF_PAD_EDGE | PF_AHEAD2)) || SUBLDS, "the pair read, its ceiling and the pads are forms of the LDS words' row");
+    static_assert(!SUBLDS2 || !(FORM & PF_KO_XOR8), "the ceiling is the single read's row");
     static_assert(!(FORM & (PF_FOLD2 | PF_CONST2)) || CELL::COLUMN, "the pair fold and the literals are the column frame's");
     static_assert(!FOLD2 || !(FORM & (PF_SINK_KEY | PF_KO_SINK | PF_KO_BOUND)), "the pair fold is the compare-and-select fold's, over the job's own rows");
     static_assert(!(FORM & PF_GE3) || (FORM & PF_CONST2), "|G_e| is the literal form's parameter");
     constexpr bool P4 = !(FORM & PF_PAT2), PBE = (FORM & PF_PBE) != 0, TBE = (FORM & PF_TBE) != 0;     // STREAM only: the host has matched them to the strings
     __shared__ uint32_t s_tab[16];           // by pattern symbol q: entry v = the pre-biased match score where v == q, the mismatch score elsewhere
-    __shared__ uint32_t s_sub[256];          // PF_SUBLDS: by sub_index of both jobs' codes nibble ^ symbol: {0, sub(c_B), 0, sub(c_A)}, sub(0) the match byte
-    if constexpr (SUBLDS)
+    __shared__ uint32_t s_sub[(FORM & PF_KO_XOR8) ? 258 : 256];   // PF_SUBLDS: by sub_index of both jobs' codes nibble ^ symbol: {0, sub(c_B), 0, sub(c_A)}, sub(0) the match byte
+    __shared__ uint2 s_sub2[1024];           // PF_SUBLDS2: by sub2_index, the words of two neighbouring cells (s_sub is not allocated then, nor s_sub2 elsewhere)
+    if constexpr (SUBLDS2)
     {
+        const uint32_t tg = uint32_t(-p.gap_ext * 32);
+        const uint32_t sm = uint32_t((p.match - p.gap_open) * 32) + tg, sx = uint32_t((p.mismatch - p.gap_open) * 32) + tg;
+        for (uint32_t k = threadIdx.x; k < 1024u; k += uint32_t(PAIR_LANES)) s_sub2[k] = make_uint2(sub2_word(k, 0u, sm, sx), sub2_word(k, 1u, sm, sx));
+    }
+    else if constexpr (SUBLDS)
+    {
+        if constexpr ((FORM & PF_KO_XOR8) != 0) { if (threadIdx.x < 2u) s_sub[256u + threadIdx.x] = 0u; }
         const uint32_t tg = uint32_t(-p.gap_ext * 32);
         const uint32_t sm = uint32_t((p.match - p.gap_open) * 32) + tg, sx = uint32_t((p.mismatch - p.gap_open) * 32) + tg;
         for (uint32_t k = threadIdx.x; k < 256u; k += uint32_t(PAIR_LANES))
@@ -765,10 +973,20 @@ banded_gotoh_pair_kernel(const GotohParams p)
     uint32_t rk2 = 0u;                                                             // PF_FOLD2: the even row's row key
     {
         const uint32_t TA = fetch16_2bit(ts[0], tb[0]), TB = fetch16_2bit(ts[1], tb[1]);
-        #pragma unroll
-        for (int j = 0; j < BAND - 1; ++j)
-            st.tc[j] = SUBLDS ? (((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 2)) << 2
-                              : CELL::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
+        if constexpr (SUBLDS2)
+        {
+            // the pairs (t, t + 1) of the band's first fourteen symbols, t = 0 ... 12, and the last of them for the first block's first pair
+            #pragma unroll
+            for (int t = 0; t < 16; ++t)
+                st.tc[t] = t < BAND - 2 ? sub2_col_byte((TA >> (2 * t)) & 3u, (TB >> (2 * t)) & 3u, (TA >> (2 * t + 2)) & 3u, (TB >> (2 * t + 2)) & 3u) << 3 : 0u;
+        }
+        else
+        {
+            #pragma unroll
+            for (int j = 0; j < BAND - 1; ++j)
+                st.tc[j] = SUBLDS ? (((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 2)) << 2
+                                  : CELL::SEL_BASE | ((TA >> (2 * j)) & 3u) | (((TB >> (2 * j)) & 3u) << 16);
+        }
     }
 
     // this block's symbols and the cursors behind them (STREAM), or the generic fetches
@@ -807,7 +1025,18 @@ banded_gotoh_pair_kernel(const GotohParams p)
             PAn = fetch_pattern16(ps[0], pb[0] + i0 + 16u); PBn = fetch_pattern16(ps[1], pb[1] + i0 + 16u);
             TAn = fetch16_2bit(ts[0], tb[0] + i0 + 16u + BAND - 1); TBn = fetch16_2bit(ts[1], tb[1] + i0 + 16u + BAND - 1);
         }
-        if constexpr (SUBLDS)
+        if constexpr (SUBLDS2)
+        {
+            uint64_t RE, RO;
+            sub2_row_words(PA, PB, RE, RO);
+            uint32_t CW[4];
+            // the symbols that entered a row before the block's first: the second of the last pair formed, (i0 + 12, i0 + 13), which slot
+            // 12 of the ring holds (in the first block from the prologue): t0 ^ d, for job A in bits 3-4 and for job B in bits 7-8
+            const uint32_t last = st.tc[12] ^ (st.tc[12] >> 2);
+            sub2_col_words(TA, TB, (last >> 3) & 3u, (last >> 7) & 3u, CW);
+            PairRows<CELL, BAND, FORM, 0, 16>::run(st, fr, i0, M, D, G, RE, RO, CW, reinterpret_cast<const uint32_t*>(s_sub2), KT, rk2);
+        }
+        else if constexpr (SUBLDS)
         {
             uint64_t RE, RO;
             sub_row_words(PA, PB, RE, RO);
@@ -834,15 +1063,21 @@ banded_gotoh_pair_kernel(const GotohParams p)
     }
 
     if constexpr (FOLD2) { if (M & 1u) CELL::template fold_last<BAND, FORM>(st, rk2, M, d32, g32); }
+    // (PF_SUBLDS2 works its job numbers out again from the lane's, one register across the block loop where the two 64-bit indices
+    // are four: they are what would not fit five waves' 96)
+    uint32_t lane_out = SUBLDS2 ? lane : 0u;
+    if constexpr (SUBLDS2) asm volatile("" : "+v"(lane_out));
+    const uint32_t id2[2] = { 2u * lane_out, 2u * lane_out + 1u < p.n ? 2u * lane_out + 1u : 2u * lane_out };
+    const uint32_t (&od)[2] = SUBLDS2 ? id2 : id;
     #pragma unroll
     for (int h = 0; h < 2; ++h)
     {
-        if (h == 1 && id[1] == id[0]) break;
+        if (h == 1 && od[1] == od[0]) break;
         // the key sink's best is score << 20 | 31 << 15 | row << 5 | column; the pair fold's is score << 5 | odd row << 4 | column beside
         // the pair's even row
         const uint32_t j = st.best[h] & (FOLD2 ? 15u : 31u), i = KEY ? (st.best[h] >> 5) & 1023u : st.besti[h] + (FOLD2 ? (st.best[h] >> 4) & 1u : 0u);
-        p.out_score[id[h]] = int32_t(st.best[h] >> (KEY ? 20 : 5));
-        reinterpret_cast<uint2*>(p.out_sink)[id[h]] = make_uint2(i + j + 1u, i + 1u);
+        p.out_score[od[h]] = int32_t(st.best[h] >> (KEY ? 20 : 5));
+        reinterpret_cast<uint2*>(p.out_sink)[od[h]] = make_uint2(i + j + 1u, i + 1u);
     }
 }
 
@@ -854,8 +1089,8 @@ hipError_t launch_band_pair(const GotohParams& p, hipStream_t stream)
     return hipGetLastError();
 }
 
-// The library's instances (NVB_PAIR_INSTANCES) are compiled in banded_gotoh_pair_b15.hip, banded_gotoh_pair_b15_lit.hip and banded_gotoh_pair_b15_sub.hip.  A translation unit that launches them and must not compile them again defines NVB_PAIR_EXTERN before
-// it includes this header: banded_gotoh.hip does; the three instantiation files, and tools/pair_row_probe.hip with its own forms, do not
+// The library's instances (NVB_PAIR_INSTANCES) are compiled in banded_gotoh_pair_b15.hip, banded_gotoh_pair_b15_lit.hip, banded_gotoh_pair_b15_sub.hip and banded_gotoh_pair_b15_sub2.hip.  A translation unit that launches them and must not compile them again defines NVB_PAIR_EXTERN before
+// it includes this header: banded_gotoh.hip does; the four instantiation files, and tools/pair_row_probe.hip with its own forms, do not
 #ifdef NVB_PAIR_EXTERN
 #define NVB_DECL(CELL, F) extern template hipError_t launch_band_pair<15, CELL, (F)>(const GotohParams&, hipStream_t);
 NVB_PAIR_INSTANCES(NVB_DECL)

@@ -11,7 +11,7 @@ namespace nvb {
 // thread-local name of the last kernel variant launched (introspection for tests/bench)
 extern thread_local const char* g_last_kernel;
 // the last banded launch, if it took the two-jobs-per-lane form (banded_gotoh_pair.h): what nvbio_hip_last_kernel_detail, _cell,
-// _fetch, _frame, _row, _const and _sub answer, which is "" unless `kernel` is still g_last_kernel
+// _fetch, _frame, _row, _const, _sub and _subread answer, which is "" unless `kernel` is still g_last_kernel
 struct PairLaunch {
     const char* kernel = nullptr;   // the g_last_kernel value of that launch, or NULL
     const char* cell   = "";        // the cell it ran, "u16" or "max3"
@@ -19,7 +19,8 @@ struct PairLaunch {
     const char* frame  = "";        // the frame its cell holds, "column" (PD3) or "row" (PM3, P16)
     const char* row    = "";        // the row around its cells, "fold2" (PD3 by default: the sink folded once per two rows) or "plain"
     const char* consts = "";        // where its cell keeps the key constants K_j, "literal" (PD3 with the pair fold by default, |G_e| <= 3) or "scalar"
-    const char* sub    = "";        // where its cell's substitution words come from, "lds" (one LDS read per cell: the literal form by default) or "perm"
+    const char* sub    = "";        // where its cell's substitution words come from, "lds" (read from an LDS table: the literal form by default) or "perm"
+    const char* subread = "";       // with "lds": the cells one LDS read serves, "pair" (two, the default) or "single" (NVBIO_HIP_PAIR_SUB = 2)
 };
 extern thread_local PairLaunch g_last_pair;
 

@@ -9,7 +9,8 @@
 // The last rows are the column frame's row with its sink folded once per two rows (PF_FOLD2), and that row with the cell's wave-uniform
 // constants in scalar registers (const-s) and as literals with the pad (PF_CONST2, const-klit-pad), and on that row the two sub-* rows:
 // the knock-out with a v_xor_b32 in each v_perm_b32's place (PF_KO_PERM, the ceiling of the lookup's class change) and the substitution
-// words read from LDS (PF_SUBLDS, sub-lds), which the library launches.  The forms that were measured beside them and are gone have
+// words read from LDS (PF_SUBLDS, sub-lds); then two cells' words to a read (sub-xor8, its ceiling, and PF_SUBLDS2, sub-lds2, which the
+// library launches) and the pad-* rows, s_nop pads at places that had none.  The forms that were measured beside them and are gone have
 // their figures in profiles/banded_pair/README.md.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/pair_row_probe.hip -o tools/pair_row_probe
@@ -82,6 +83,7 @@ struct Variant { const char* name; const char* what; hipError_t (*launch)(const 
 #define FORM(f) launch_band_pair<15, PM3, (f)>
 #define COLF(f) launch_band_pair<15, PD3, (f)>
 constexpr int STREAMED = PF_STREAM | PF_PBE;               // the streamed form of these strings: 4-bit big-endian reads, little-endian windows
+constexpr int SUBLDS = STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1 | PF_SUBLDS;   // sub-lds's form
 static const Variant VARIANTS[] = {
     { "K0",        "nothing: generic fetches (the form before the streamed one)",      FORM(PF_SINK_VCC), READ, true },
     { "K1",        "the sink fold",                                                    FORM(PF_KO_SINK), READ, false },
@@ -114,6 +116,21 @@ static const Variant VARIANTS[] = {
     { "sub-xor",    "const-klit-pad, a v_xor_b32 for each v_perm_b32, table reads kept", COLF(STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1 | PF_KO_PERM), READ, false },
     { "sub-lds",    "const-klit-pad, substitution words from LDS (PF_SUBLDS)",         COLF(STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1 | PF_SUBLDS), READ, true },
     { "sub-perm'",  "const-klit-pad once more (the run's drift)",                      COLF(STREAMED | PF_FOLD2 | PF_CONST2 | PF_GE1), READ, true },
+    // two cells per read, on sub-lds's row: the ceiling (a knock-out: eight address xors and eight reads of two adjacent words of
+    // sub-lds's table, so seven cells of a row take a wrong word), the form itself (PF_SUBLDS2, ds_read_b64 from a table of 1 024 pairs),
+    // whose checksum must be sub-lds's, and sub-lds once more
+    { "sub-xor8",   "sub-lds, 8 address xors and 8 two-word reads per row",            COLF(SUBLDS | PF_KO_XOR8), READ, false },
+    { "sub-lds2",   "sub-lds, two cells per read (PF_SUBLDS2, the library's launch)",  COLF(SUBLDS | PF_SUBLDS2), READ, true },
+    { "sub-lds2-a2","sub-lds2, the reads two pairs ahead of the cells (one VGPR spilled)", COLF(SUBLDS | PF_SUBLDS2 | PF_AHEAD2), READ, true },
+    { "sub-lds'",   "sub-lds once more (the run's drift)",                             COLF(SUBLDS), READ, true },
+    // pads that were never tried, on both LDS rows: one s_nop behind each run of address xors (padx); PF_CONST2's pad behind the
+    // groups of simple ops in col0 and tail2 as well (pade)
+    { "pad-lds-x",  "sub-lds, an s_nop behind each run of address xors",               COLF(SUBLDS | PF_PAD_XOR), READ, true },
+    { "pad-lds-e",  "sub-lds, s_nop pads in col0 and tail2",                           COLF(SUBLDS | PF_PAD_EDGE), READ, true },
+    { "pad-lds2-x", "sub-lds2, an s_nop behind each run of address xors",              COLF(SUBLDS | PF_SUBLDS2 | PF_PAD_XOR), READ, true },
+    { "pad-lds2-e", "sub-lds2, s_nop pads in col0 and tail2",                          COLF(SUBLDS | PF_SUBLDS2 | PF_PAD_EDGE), READ, true },
+    { "pad-lds2-xe","sub-lds2, both pads",                                             COLF(SUBLDS | PF_SUBLDS2 | PF_PAD_XOR | PF_PAD_EDGE), READ, true },
+    { "sub-lds2'",  "sub-lds2 once more (the run's drift)",                            COLF(SUBLDS | PF_SUBLDS2), READ, true },
 };
 
 int main(int argc, char** argv)
