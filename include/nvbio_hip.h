@@ -1103,6 +1103,104 @@ int nvbio_hip_set_suffix_sort_host(const nvbio_hip_string_set* set, uint32_t n_s
 int nvbio_hip_set_bwt_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint64_t n_suffixes, uint8_t* bwt_out,
                            uint32_t* dollar_rows_out, uint32_t* dollar_ids_out, uint32_t* suffixes_out, int32_t n_threads);
 
+/* ---- Q-gram indices and the q-gram filter (nvbio/qgram/qgram.h: QGramIndexDevice, QGramSetIndexDevice, generate_qgrams;
+ * nvbio/qgram/filter.h: QGramFilterDevice::rank / locate / merge).
+ * Q-gram: over 2-bit symbols, 1 <= q <= 32, the q-gram at position i of a string of len symbols is the 64-bit word
+ * sum_j sym(i + j) << 2j, j < q: the first symbol in the lowest bits, sym = 0 where i + j >= len (a truncated q-gram at the tail is
+ * padded with A), and 0 where i >= len.  Q-grams are ordered as these integers, which is not the strings' lexicographic order.
+ * Index: qgrams[n_unique] = the distinct q-grams, ascending; slots[n_unique + 1] = the exclusive sums of their counts,
+ * slots[n_unique] = n_qgrams; index[n_qgrams] = the coordinates grouped by q-gram, inside one q-gram in enumeration order.  A string
+ * index has one coordinate per position 0 .. len - 1 (the q - 1 truncated ones included), a uint32; a set index has the uint2
+ * (string id, pos) for pos = 0, interval, .. while pos + q <= length[id], enumerated by string id and then by pos.  With QL = ql > 0,
+ * lut[4^QL + 1]: lut[k] = the lower bound of k << 2 (q - QL) in qgrams, lut[4^QL] = n_unique.  0 <= ql <= min(q, 16).
+ * Limits: bits == 2, n_words >= 1, at most 0xFFFFFFFF q-grams.  A violation, a null pointer or too little temp return
+ * hipErrorInvalidValue and launch nothing.  Nothing is allocated inside: temp is device scratch of the matching _temp_bytes.
+ * Scratch of a build over n q-grams of a set of N strings: keys A (8 n) | keys B (8 n) | coordinates in enumeration order (4 n; 8 n
+ * for a set) | run counts (4 n) | the run count (256) | for a set, the 64-bit inclusive sums of the per-string seed counts (8 N) |
+ * rocPRIM's; rank: rocPRIM's scan; merge: keys A | keys B (4 n each; 8 n for a set) | the run count (256) | rocPRIM's.
+ * The builds, rank, merge and count_seeds with a length array wait for the stream (for n_unique, the total, n_merged, the count) and
+ * have finished when they return; generate, range and locate are asynchronous. */
+typedef struct nvbio_hip_qgram_index {
+    const uint64_t* qgrams;     /* [n_unique] */
+    const uint32_t* slots;      /* [n_unique + 1] */
+    const uint32_t* index;      /* [n_qgrams] uint32, or [n_qgrams] uint2 for a set index */
+    const uint32_t* lut;        /* [4^ql + 1], or NULL when ql == 0 */
+    uint32_t        q, ql;
+    uint32_t        n_unique, n_qgrams;
+} nvbio_hip_qgram_index;
+
+/* qgrams_out[i] = the q-gram at positions[i] of the string of len symbols that starts at symbol 0 of words; positions == NULL means
+ * position i.  The set form takes n (string id, pos) pairs; an id >= n_strings gives 0. */
+int nvbio_hip_qgram_generate(const uint32_t* words, uint64_t n_words, uint32_t bits, uint32_t big_endian, uint64_t len, uint32_t q,
+                             const uint32_t* positions /* [n] or NULL */, uint64_t n, uint64_t* qgrams_out /* [n] */, void* stream);
+int nvbio_hip_qgram_set_generate(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, const uint32_t* coords /* [2 n] */, uint64_t n,
+                                 uint64_t* qgrams_out /* [n] */, void* stream);
+uint64_t nvbio_hip_qgram_index_build_temp_bytes(uint64_t len);
+int nvbio_hip_qgram_index_build(const uint32_t* words, uint64_t n_words, uint32_t bits, uint32_t big_endian, uint64_t len, uint32_t q, uint32_t ql,
+                                uint64_t* qgrams_out /* [len] */, uint32_t* slots_out /* [len + 1] */, uint32_t* index_out /* [len] */,
+                                uint32_t* lut_out /* [4^ql + 1]; NULL when ql == 0 */, uint32_t* n_unique_out /* host */,
+                                void* temp, uint64_t temp_bytes, void* stream);
+/* *n_qgrams_out (host) = the seeds of uniform_seeds_functor(q, interval) over the set; with fixed_length nothing is launched and temp
+ * may be NULL. */
+uint64_t nvbio_hip_qgram_set_count_seeds_temp_bytes(uint32_t n_strings);
+int nvbio_hip_qgram_set_count_seeds(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, uint32_t interval, uint64_t* n_qgrams_out,
+                                    void* temp, uint64_t temp_bytes, void* stream);
+/* n_qgrams: the seed count the caller sized the buffers for; it is checked before anything but the scratch is written, and a wrong one
+ * returns hipErrorInvalidValue.  index_out holds uint2 (string id, pos). */
+uint64_t nvbio_hip_qgram_set_index_build_temp_bytes(uint64_t n_qgrams, uint32_t n_strings);
+int nvbio_hip_qgram_set_index_build(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, uint32_t interval, uint32_t ql, uint64_t n_qgrams,
+                                    uint64_t* qgrams_out /* [n_qgrams] */, uint32_t* slots_out /* [n_qgrams + 1] */, uint32_t* index_out /* [2 n_qgrams] */,
+                                    uint32_t* lut_out, uint32_t* n_unique_out /* host */, void* temp, uint64_t temp_bytes, void* stream);
+/* ranges_out[i] = the uint2 (slots[k], slots[k + 1]) of queries[i] = qgrams[k], (0, 0) where the q-gram is not in the index: the LUT
+ * bucket if there is one, a lower bound inside it, two slot reads.  index->index is not read. */
+int nvbio_hip_qgram_range(const nvbio_hip_qgram_index* index, const uint64_t* queries, uint64_t n_queries, uint32_t* ranges_out /* [2 n] */, void* stream);
+/* the filter's rank: the ranges, slots_out = the inclusive 64-bit sums of their sizes, *total_out (host) = the last sum, 0 for no
+ * queries */
+uint64_t nvbio_hip_qgram_rank_temp_bytes(uint64_t n_queries);
+int nvbio_hip_qgram_rank(const nvbio_hip_qgram_index* index, const uint64_t* queries, uint64_t n_queries, uint32_t* ranges_out /* [2 n] */,
+                         uint64_t* slots_out /* [n] */, uint64_t* total_out, void* temp, uint64_t temp_bytes, void* stream);
+/* the filter's locate over the outputs [begin, end): for output o, slot = the upper bound of o in slots, local = o - slots[slot - 1]
+ * (64 bits), hit = (index[ranges[slot].x + local], indices[slot]): a uint2 (qgram pos, query idx) for a string index, a uint4
+ * (string id, pos, query idx, 0) for a set index.  An output at or past the total gives a zero hit. */
+int nvbio_hip_qgram_locate(const nvbio_hip_qgram_index* index, uint32_t n_queries, const uint32_t* ranges, const uint64_t* slots,
+                           const uint32_t* indices /* [n_queries] */, uint64_t begin, uint64_t end, uint32_t* hits_out /* [2 (end - begin)] */, void* stream);
+int nvbio_hip_qgram_set_locate(const nvbio_hip_qgram_index* index, uint32_t n_queries, const uint32_t* ranges, const uint64_t* slots,
+                               const uint32_t* indices, uint64_t begin, uint64_t end, uint32_t* hits_out /* [4 (end - begin)] */, void* stream);
+/* the filter's merge: diag = query idx - index pos in wrapping uint32, snapped as the reference's util::round(diag, interval) does it:
+ * r = (diag / interval) * interval, and r + 1 (one, not interval) where uint32((diag - r) * 2) > interval.  The key of a string hit is
+ * that word; of a set hit the uint2 (snapped diag, string id), ordered with the string id in the high half.  merged_out = the distinct
+ * keys ascending, counts_out their counts, *n_merged_out (host) their number.  interval >= 1. */
+uint64_t nvbio_hip_qgram_merge_temp_bytes(uint32_t n_hits);
+int nvbio_hip_qgram_merge(const uint32_t* hits /* [2 n_hits] */, uint32_t n_hits, uint32_t interval, uint32_t* merged_out /* [n_hits] */,
+                          uint32_t* counts_out /* [n_hits] */, uint32_t* n_merged_out, void* temp, uint64_t temp_bytes, void* stream);
+uint64_t nvbio_hip_qgram_set_merge_temp_bytes(uint32_t n_hits);
+int nvbio_hip_qgram_set_merge(const uint32_t* hits /* [4 n_hits] */, uint32_t n_hits, uint32_t interval, uint32_t* merged_out /* [2 n_hits] */,
+                              uint32_t* counts_out /* [n_hits] */, uint32_t* n_merged_out, void* temp, uint64_t temp_bytes, void* stream);
+/* The host twins: host pointers everywhere, a thread count instead of scratch and stream, the same bytes. */
+int nvbio_hip_qgram_generate_host(const uint32_t* words, uint64_t n_words, uint32_t bits, uint32_t big_endian, uint64_t len, uint32_t q,
+                                  const uint32_t* positions, uint64_t n, uint64_t* qgrams_out, int32_t n_threads);
+int nvbio_hip_qgram_set_generate_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, const uint32_t* coords, uint64_t n,
+                                      uint64_t* qgrams_out, int32_t n_threads);
+int nvbio_hip_qgram_index_build_host(const uint32_t* words, uint64_t n_words, uint32_t bits, uint32_t big_endian, uint64_t len, uint32_t q, uint32_t ql,
+                                     uint64_t* qgrams_out, uint32_t* slots_out, uint32_t* index_out, uint32_t* lut_out, uint32_t* n_unique_out,
+                                     int32_t n_threads);
+int nvbio_hip_qgram_set_count_seeds_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, uint32_t interval, uint64_t* n_qgrams_out,
+                                         int32_t n_threads);
+int nvbio_hip_qgram_set_index_build_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, uint32_t interval, uint32_t ql, uint64_t n_qgrams,
+                                         uint64_t* qgrams_out, uint32_t* slots_out, uint32_t* index_out, uint32_t* lut_out, uint32_t* n_unique_out,
+                                         int32_t n_threads);
+int nvbio_hip_qgram_range_host(const nvbio_hip_qgram_index* index, const uint64_t* queries, uint64_t n_queries, uint32_t* ranges_out, int32_t n_threads);
+int nvbio_hip_qgram_rank_host(const nvbio_hip_qgram_index* index, const uint64_t* queries, uint64_t n_queries, uint32_t* ranges_out,
+                              uint64_t* slots_out, uint64_t* total_out, int32_t n_threads);
+int nvbio_hip_qgram_locate_host(const nvbio_hip_qgram_index* index, uint32_t n_queries, const uint32_t* ranges, const uint64_t* slots,
+                                const uint32_t* indices, uint64_t begin, uint64_t end, uint32_t* hits_out, int32_t n_threads);
+int nvbio_hip_qgram_set_locate_host(const nvbio_hip_qgram_index* index, uint32_t n_queries, const uint32_t* ranges, const uint64_t* slots,
+                                    const uint32_t* indices, uint64_t begin, uint64_t end, uint32_t* hits_out, int32_t n_threads);
+int nvbio_hip_qgram_merge_host(const uint32_t* hits, uint32_t n_hits, uint32_t interval, uint32_t* merged_out, uint32_t* counts_out,
+                               uint32_t* n_merged_out, int32_t n_threads);
+int nvbio_hip_qgram_set_merge_host(const uint32_t* hits, uint32_t n_hits, uint32_t interval, uint32_t* merged_out, uint32_t* counts_out,
+                                   uint32_t* n_merged_out, int32_t n_threads);
+
 /* Device-memory helpers for host code that has no HIP headers (the C++ host layer in
  * include/nvbio_hip/ uses them where the reference uses thrust::device_vector).
  * kind: 1 = host->device, 2 = device->host, 3 = device->device. */

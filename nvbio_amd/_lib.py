@@ -36,6 +36,13 @@ SYMBOLS = [
     "nvbio_hip_suffix_sort_host", "nvbio_hip_bwt_host",
     "nvbio_hip_set_suffix_sort_temp_bytes", "nvbio_hip_set_suffix_sort", "nvbio_hip_set_bwt_temp_bytes", "nvbio_hip_set_bwt",
     "nvbio_hip_set_suffix_sort_host", "nvbio_hip_set_bwt_host",
+    "nvbio_hip_qgram_generate", "nvbio_hip_qgram_set_generate", "nvbio_hip_qgram_index_build_temp_bytes", "nvbio_hip_qgram_index_build",
+    "nvbio_hip_qgram_set_count_seeds_temp_bytes", "nvbio_hip_qgram_set_count_seeds", "nvbio_hip_qgram_set_index_build_temp_bytes", "nvbio_hip_qgram_set_index_build",
+    "nvbio_hip_qgram_range", "nvbio_hip_qgram_rank_temp_bytes", "nvbio_hip_qgram_rank", "nvbio_hip_qgram_locate", "nvbio_hip_qgram_set_locate",
+    "nvbio_hip_qgram_merge_temp_bytes", "nvbio_hip_qgram_merge", "nvbio_hip_qgram_set_merge_temp_bytes", "nvbio_hip_qgram_set_merge",
+    "nvbio_hip_qgram_generate_host", "nvbio_hip_qgram_set_generate_host", "nvbio_hip_qgram_index_build_host", "nvbio_hip_qgram_set_count_seeds_host",
+    "nvbio_hip_qgram_set_index_build_host", "nvbio_hip_qgram_range_host", "nvbio_hip_qgram_rank_host", "nvbio_hip_qgram_locate_host",
+    "nvbio_hip_qgram_set_locate_host", "nvbio_hip_qgram_merge_host", "nvbio_hip_qgram_set_merge_host",
     "nvbio_hip_device_malloc", "nvbio_hip_device_free", "nvbio_hip_device_free_ordered", "nvbio_hip_device_free_after", "nvbio_hip_device_trim", "nvbio_hip_device_mem_info", "nvbio_hip_memcpy", "nvbio_hip_memset",
     "nvbio_hip_stream_synchronize", "nvbio_hip_stream_query", "nvbio_hip_host_malloc", "nvbio_hip_host_free", "nvbio_hip_stream_create", "nvbio_hip_stream_destroy",
     "nvbio_hip_comm_available", "nvbio_hip_device_count", "nvbio_hip_set_device", "nvbio_hip_get_device", "nvbio_hip_comm_unique_id", "nvbio_hip_comm_init_rank",
@@ -52,6 +59,11 @@ class PeParamsStruct(C.Structure):       # nvbio_hip_pe_params
 class StringSetStruct(C.Structure):      # nvbio_hip_string_set
     _fields_ = [("words", C.c_void_p), ("n_words", C.c_uint64), ("bits", C.c_uint32), ("big_endian", C.c_uint32),
                 ("begin", C.c_void_p), ("length", C.c_void_p), ("fixed_length", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class QGramIndexStruct(C.Structure):     # nvbio_hip_qgram_index
+    _fields_ = [("qgrams", C.c_void_p), ("slots", C.c_void_p), ("index", C.c_void_p), ("lut", C.c_void_p),
+                ("q", C.c_uint32), ("ql", C.c_uint32), ("n_unique", C.c_uint32), ("n_qgrams", C.c_uint32)]
 
 
 class GotohSchemeStruct(C.Structure):    # nvbio_hip_gotoh_scheme
@@ -249,6 +261,37 @@ def lib():
         L.nvbio_hip_set_bwt.argtypes = [P(StringSetStruct), u32, u64, vp, vp, vp, vp, vp, u64, vp]
         L.nvbio_hip_set_suffix_sort_host.argtypes = [P(StringSetStruct), u32, u64, vp, vp, vp, i32]
         L.nvbio_hip_set_bwt_host.argtypes = [P(StringSetStruct), u32, u64, vp, vp, vp, vp, i32]
+        QI, SS = P(QGramIndexStruct), P(StringSetStruct)
+        L.nvbio_hip_qgram_generate.argtypes = [vp, u64, u32, u32, u64, u32, vp, u64, vp, vp]
+        L.nvbio_hip_qgram_set_generate.argtypes = [SS, u32, u32, vp, u64, vp, vp]
+        L.nvbio_hip_qgram_index_build_temp_bytes.argtypes = [u64]
+        L.nvbio_hip_qgram_index_build.argtypes = [vp, u64, u32, u32, u64, u32, u32, vp, vp, vp, vp, P(u32), vp, u64, vp]
+        L.nvbio_hip_qgram_set_count_seeds_temp_bytes.argtypes = [u32]
+        L.nvbio_hip_qgram_set_count_seeds.argtypes = [SS, u32, u32, u32, P(u64), vp, u64, vp]
+        L.nvbio_hip_qgram_set_index_build_temp_bytes.argtypes = [u64, u32]
+        L.nvbio_hip_qgram_set_index_build.argtypes = [SS, u32, u32, u32, u32, u64, vp, vp, vp, vp, P(u32), vp, u64, vp]
+        L.nvbio_hip_qgram_range.argtypes = [QI, vp, u64, vp, vp]
+        L.nvbio_hip_qgram_rank_temp_bytes.argtypes = [u64]
+        L.nvbio_hip_qgram_rank.argtypes = [QI, vp, u64, vp, vp, P(u64), vp, u64, vp]
+        L.nvbio_hip_qgram_locate.argtypes = [QI, u32, vp, vp, vp, u64, u64, vp, vp]
+        L.nvbio_hip_qgram_set_locate.argtypes = [QI, u32, vp, vp, vp, u64, u64, vp, vp]
+        L.nvbio_hip_qgram_merge_temp_bytes.argtypes = [u32]
+        L.nvbio_hip_qgram_merge.argtypes = [vp, u32, u32, vp, vp, P(u32), vp, u64, vp]
+        L.nvbio_hip_qgram_set_merge_temp_bytes.argtypes = [u32]
+        L.nvbio_hip_qgram_set_merge.argtypes = [vp, u32, u32, vp, vp, P(u32), vp, u64, vp]
+        for f in ("index_build", "set_count_seeds", "set_index_build", "rank", "merge", "set_merge"):
+            getattr(L, "nvbio_hip_qgram_%s_temp_bytes" % f).restype = u64
+        L.nvbio_hip_qgram_generate_host.argtypes = [vp, u64, u32, u32, u64, u32, vp, u64, vp, i32]
+        L.nvbio_hip_qgram_set_generate_host.argtypes = [SS, u32, u32, vp, u64, vp, i32]
+        L.nvbio_hip_qgram_index_build_host.argtypes = [vp, u64, u32, u32, u64, u32, u32, vp, vp, vp, vp, P(u32), i32]
+        L.nvbio_hip_qgram_set_count_seeds_host.argtypes = [SS, u32, u32, u32, P(u64), i32]
+        L.nvbio_hip_qgram_set_index_build_host.argtypes = [SS, u32, u32, u32, u32, u64, vp, vp, vp, vp, P(u32), i32]
+        L.nvbio_hip_qgram_range_host.argtypes = [QI, vp, u64, vp, i32]
+        L.nvbio_hip_qgram_rank_host.argtypes = [QI, vp, u64, vp, vp, P(u64), i32]
+        L.nvbio_hip_qgram_locate_host.argtypes = [QI, u32, vp, vp, vp, u64, u64, vp, i32]
+        L.nvbio_hip_qgram_set_locate_host.argtypes = [QI, u32, vp, vp, vp, u64, u64, vp, i32]
+        L.nvbio_hip_qgram_merge_host.argtypes = [vp, u32, u32, vp, vp, P(u32), i32]
+        L.nvbio_hip_qgram_set_merge_host.argtypes = [vp, u32, u32, vp, vp, P(u32), i32]
         L.nvbio_hip_comm_unique_id.argtypes = [vp]
         L.nvbio_hip_comm_init_rank.argtypes = [P(vp), C.c_int, C.c_int, vp]
         L.nvbio_hip_comm_init_all.argtypes = [vp, C.c_int, vp]

@@ -592,3 +592,277 @@ NVB_API int nvbio_hip_set_bwt_host(const nvbio_hip_string_set* set, uint32_t n_s
     }
     return hipSuccess;
 }
+
+// ---- q-gram indices and the q-gram filter (qgram.hip): the definitions of include/nvbio_hip.h symbol by symbol, std::stable_sort for
+// the build and std::sort for merge -- all orders are total, so the same bytes ----
+namespace {
+
+inline bool qgram_params_ok(const uint32 bits, const uint32 q, const uint32 ql) { return bits == 2u && q >= 1u && q <= 32u && ql <= (q < 16u ? q : 16u); }
+inline bool qgram_set_ok(const nvbio_hip_string_set* set, const uint32 n_strings)
+{
+    return set && set->words && set->n_words && (set->begin || n_strings == 0u) && set->bits == 2u;
+}
+inline int qgram_threads(const int32 n_threads)
+{
+#if defined(_OPENMP)
+    return n_threads > 0 ? n_threads : omp_get_max_threads();
+#else
+    return 1;
+#endif
+}
+
+/// the q-gram at position pos of the string [begin, begin + len): only symbols of the string are read
+inline uint64 qgram_at(const uint32* words, const uint32 be, const uint64 begin, const uint64 len, const uint64 pos, const uint32 q)
+{
+    uint64 g = 0;
+    for (uint32 j = 0; j < q && pos + j < len; ++j)
+        g |= uint64(text_symbol(words, be, begin + pos + j)) << (2u * j);
+    return g;
+}
+
+inline uint64 qgram_seed_count(const uint32 len, const uint32 q, const uint32 interval) { return len >= q ? uint64(len - q) / interval + 1u : 0u; }
+
+/// keys / coords in enumeration order -> the index arrays
+template <typename V>
+void qgram_build_host(const std::vector<uint64>& keys, const V* coords, const uint32 q, const uint32 ql, uint64* qgrams_out, uint32* slots_out,
+                      V* index_out, uint32* lut_out, uint32* n_unique_out)
+{
+    const uint64 n = keys.size();
+    std::vector<uint32> order(n);
+    for (uint64 i = 0; i < n; ++i) order[i] = uint32(i);
+    std::stable_sort(order.begin(), order.end(), [&](const uint32 a, const uint32 b) { return keys[a] < keys[b]; });
+    uint32 n_unique = 0;
+    for (uint64 k = 0; k < n; ++k)
+    {
+        if (k == 0 || keys[order[k]] != keys[order[k - 1u]]) { qgrams_out[n_unique] = keys[order[k]]; slots_out[n_unique] = uint32(k); ++n_unique; }
+        index_out[k] = coords[order[k]];
+    }
+    slots_out[n_unique] = uint32(n);
+    if (ql)
+    {
+        const uint64 n_keys = 1ull << (2u * ql);
+        for (uint64 k = 0; k < n_keys; ++k)
+            lut_out[k] = uint32(std::lower_bound(qgrams_out, qgrams_out + n_unique, k << (2u * (q - ql))) - qgrams_out);
+        lut_out[n_keys] = n_unique;
+    }
+    *n_unique_out = n_unique;
+}
+
+inline bool qgram_index_ok(const nvbio_hip_qgram_index* ix)
+{
+    if (!ix || !ix->slots || !qgram_params_ok(2u, ix->q, ix->ql) || ix->n_unique > ix->n_qgrams) return false;
+    if (ix->n_unique && !ix->qgrams) return false;
+    if (ix->ql && !ix->lut) return false;
+    return true;
+}
+
+inline void qgram_range_of(const nvbio_hip_qgram_index* ix, const uint64 g, uint32* out)
+{
+    out[0] = out[1] = 0u;
+    if (ix->q < 32u && (g >> (2u * ix->q))) return;
+    uint32 lo = 0u, hi = ix->n_unique;
+    if (ix->ql) { const uint64 k = g >> (2u * (ix->q - ix->ql)); lo = ix->lut[k]; hi = ix->lut[k + 1u]; }
+    const uint32 i = uint32(std::lower_bound(ix->qgrams + lo, ix->qgrams + hi, g) - ix->qgrams);
+    if (i >= ix->n_unique || ix->qgrams[i] != g) return;
+    out[0] = ix->slots[i]; out[1] = ix->slots[i + 1u];
+}
+
+template <bool SET>
+int qgram_locate_host(const nvbio_hip_qgram_index* ix, const uint32 n_queries, const uint32* ranges, const uint64* slots, const uint32* indices,
+                      const uint64 begin, const uint64 end, uint32* hits, const int32 n_threads)
+{
+    if (!qgram_index_ok(ix) || begin > end) return hipErrorInvalidValue;
+    if (begin == end) return hipSuccess;
+    if (n_queries == 0u || !ranges || !slots || !indices || !hits || !ix->index) return hipErrorInvalidValue;
+    const int threads = qgram_threads(n_threads);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 k = 0; k < int64(end - begin); ++k)
+    {
+        const uint64 o = begin + uint64(k);
+        const uint32 slot = uint32(std::upper_bound(slots, slots + n_queries, o) - slots);
+        uint32 h0 = 0u, h1 = 0u, h2 = 0u;
+        if (slot < n_queries)
+        {
+            const uint64 at = uint64(ranges[2u * slot]) + (o - (slot ? slots[slot - 1u] : 0ull));
+            if (at < ix->n_qgrams)
+            {
+                if (SET) { h0 = ix->index[2u * at]; h1 = ix->index[2u * at + 1u]; h2 = indices[slot]; }
+                else     { h0 = ix->index[at]; h1 = indices[slot]; }
+            }
+        }
+        if (SET) { hits[4 * k] = h0; hits[4 * k + 1] = h1; hits[4 * k + 2] = h2; hits[4 * k + 3] = 0u; }
+        else     { hits[2 * k] = h0; hits[2 * k + 1] = h1; }
+    }
+    return hipSuccess;
+}
+
+inline uint32 qgram_snap(const uint32 diag, const uint32 interval)
+{
+    const uint32 r = (diag / interval) * interval;
+    return uint32((diag - r) * 2u) > interval ? r + 1u : r;
+}
+
+template <typename K>
+void qgram_merge_keys(std::vector<K>& keys, K* merged_out, uint32* counts_out, uint32* n_merged_out)
+{
+    std::sort(keys.begin(), keys.end());
+    uint32 m = 0;
+    for (size_t k = 0; k < keys.size(); ++k)
+    {
+        if (k == 0 || keys[k] != keys[k - 1u]) { merged_out[m] = keys[k]; counts_out[m] = 0u; ++m; }
+        ++counts_out[m - 1u];
+    }
+    *n_merged_out = m;
+}
+
+} // anonymous namespace
+
+NVB_API int nvbio_hip_qgram_generate_host(const uint32_t* words, uint64_t n_words, uint32_t bits, uint32_t big_endian, uint64_t len, uint32_t q,
+                                          const uint32_t* positions, uint64_t n, uint64_t* qgrams_out, int32_t n_threads)
+{
+    if (!words || !n_words || !qgram_params_ok(bits, q, 0u) || len > 0xFFFFFFFFull || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (n == 0u) return hipSuccess;
+    if (!qgrams_out) return hipErrorInvalidValue;
+    const int threads = qgram_threads(n_threads);
+    const uint32 be = big_endian ? 1u : 0u;
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 i = 0; i < int64(n); ++i)
+        qgrams_out[i] = qgram_at(words, be, 0u, len, positions ? positions[i] : uint64(i), q);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_set_generate_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, const uint32_t* coords, uint64_t n,
+                                              uint64_t* qgrams_out, int32_t n_threads)
+{
+    if (!qgram_set_ok(set, n_strings) || !qgram_params_ok(2u, q, 0u) || n > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (n == 0u) return hipSuccess;
+    if (!coords || !qgrams_out) return hipErrorInvalidValue;
+    const int threads = qgram_threads(n_threads);
+    const uint32 be = set->big_endian ? 1u : 0u;
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 i = 0; i < int64(n); ++i)
+    {
+        const uint32 id = coords[2 * i], pos = coords[2 * i + 1];
+        qgrams_out[i] = id < n_strings ? qgram_at(set->words, be, set->begin[id], set_length(set, id), pos, q) : 0ull;
+    }
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_index_build_host(const uint32_t* words, uint64_t n_words, uint32_t bits, uint32_t big_endian, uint64_t len, uint32_t q, uint32_t ql,
+                                             uint64_t* qgrams_out, uint32_t* slots_out, uint32_t* index_out, uint32_t* lut_out, uint32_t* n_unique_out,
+                                             int32_t n_threads)
+{
+    if (!words || !n_words || !qgram_params_ok(bits, q, ql) || len > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (!slots_out || !n_unique_out || (len && (!qgrams_out || !index_out)) || (ql && !lut_out)) return hipErrorInvalidValue;
+    const int threads = qgram_threads(n_threads);
+    const uint32 be = big_endian ? 1u : 0u;
+    std::vector<uint64> keys(len);
+    std::vector<uint32> coords(len);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 i = 0; i < int64(len); ++i) { keys[i] = qgram_at(words, be, 0u, len, uint64(i), q); coords[i] = uint32(i); }
+    qgram_build_host<uint32>(keys, coords.data(), q, ql, qgrams_out, slots_out, index_out, lut_out, n_unique_out);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_set_count_seeds_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, uint32_t interval, uint64_t* n_qgrams_out,
+                                                 int32_t n_threads)
+{
+    (void)n_threads;
+    if (!qgram_set_ok(set, n_strings) || !qgram_params_ok(2u, q, 0u) || interval == 0u || !n_qgrams_out) return hipErrorInvalidValue;
+    uint64 total = 0;
+    for (uint32 s = 0; s < n_strings; ++s) total += qgram_seed_count(set_length(set, s), q, interval);
+    *n_qgrams_out = total;
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_set_index_build_host(const nvbio_hip_string_set* set, uint32_t n_strings, uint32_t q, uint32_t interval, uint32_t ql,
+                                                 uint64_t n_qgrams, uint64_t* qgrams_out, uint32_t* slots_out, uint32_t* index_out, uint32_t* lut_out,
+                                                 uint32_t* n_unique_out, int32_t n_threads)
+{
+    (void)n_threads;
+    if (!qgram_set_ok(set, n_strings) || !qgram_params_ok(2u, q, ql) || interval == 0u || n_qgrams > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (!slots_out || !n_unique_out || (n_qgrams && (!qgrams_out || !index_out)) || (ql && !lut_out)) return hipErrorInvalidValue;
+    uint64 total = 0;
+    for (uint32 s = 0; s < n_strings; ++s) total += qgram_seed_count(set_length(set, s), q, interval);
+    if (total != n_qgrams) return hipErrorInvalidValue;
+    const uint32 be = set->big_endian ? 1u : 0u;
+    std::vector<uint64> keys, coords;
+    keys.reserve(n_qgrams); coords.reserve(n_qgrams);
+    for (uint32 s = 0; s < n_strings; ++s)
+    {
+        const uint32 len = set_length(set, s);
+        for (uint64 pos = 0; pos + q <= len; pos += interval)
+        {
+            keys.push_back(qgram_at(set->words, be, set->begin[s], len, pos, q));
+            coords.push_back((pos << 32) | s);
+        }
+    }
+    qgram_build_host<uint64>(keys, coords.data(), q, ql, qgrams_out, slots_out, reinterpret_cast<uint64*>(index_out), lut_out, n_unique_out);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_range_host(const nvbio_hip_qgram_index* index, const uint64_t* queries, uint64_t n_queries, uint32_t* ranges_out, int32_t n_threads)
+{
+    if (!qgram_index_ok(index) || n_queries > 0xFFFFFFFFull) return hipErrorInvalidValue;
+    if (n_queries == 0u) return hipSuccess;
+    if (!queries || !ranges_out) return hipErrorInvalidValue;
+    const int threads = qgram_threads(n_threads);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 i = 0; i < int64(n_queries); ++i) qgram_range_of(index, queries[i], ranges_out + 2 * i);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_rank_host(const nvbio_hip_qgram_index* index, const uint64_t* queries, uint64_t n_queries, uint32_t* ranges_out,
+                                      uint64_t* slots_out, uint64_t* total_out, int32_t n_threads)
+{
+    if (!qgram_index_ok(index) || n_queries > 0xFFFFFFFFull || !total_out) return hipErrorInvalidValue;
+    if (n_queries == 0u) { *total_out = 0u; return hipSuccess; }
+    if (!queries || !ranges_out || !slots_out) return hipErrorInvalidValue;
+    if (int e = nvbio_hip_qgram_range_host(index, queries, n_queries, ranges_out, n_threads)) return e;
+    uint64 sum = 0;
+    for (uint64 i = 0; i < n_queries; ++i) { sum += uint64(ranges_out[2 * i + 1] - ranges_out[2 * i]); slots_out[i] = sum; }
+    *total_out = sum;
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_locate_host(const nvbio_hip_qgram_index* index, uint32_t n_queries, const uint32_t* ranges, const uint64_t* slots,
+                                        const uint32_t* indices, uint64_t begin, uint64_t end, uint32_t* hits_out, int32_t n_threads)
+{
+    return qgram_locate_host<false>(index, n_queries, ranges, slots, indices, begin, end, hits_out, n_threads);
+}
+
+NVB_API int nvbio_hip_qgram_set_locate_host(const nvbio_hip_qgram_index* index, uint32_t n_queries, const uint32_t* ranges, const uint64_t* slots,
+                                            const uint32_t* indices, uint64_t begin, uint64_t end, uint32_t* hits_out, int32_t n_threads)
+{
+    return qgram_locate_host<true>(index, n_queries, ranges, slots, indices, begin, end, hits_out, n_threads);
+}
+
+NVB_API int nvbio_hip_qgram_merge_host(const uint32_t* hits, uint32_t n_hits, uint32_t interval, uint32_t* merged_out, uint32_t* counts_out,
+                                       uint32_t* n_merged_out, int32_t n_threads)
+{
+    (void)n_threads;
+    if (interval == 0u || !n_merged_out) return hipErrorInvalidValue;
+    if (n_hits == 0u) { *n_merged_out = 0u; return hipSuccess; }
+    if (!hits || !merged_out || !counts_out) return hipErrorInvalidValue;
+    std::vector<uint32> keys(n_hits);
+    for (uint32 i = 0; i < n_hits; ++i) keys[i] = qgram_snap(hits[2u * uint64(i) + 1u] - hits[2u * uint64(i)], interval);
+    qgram_merge_keys<uint32>(keys, merged_out, counts_out, n_merged_out);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_qgram_set_merge_host(const uint32_t* hits, uint32_t n_hits, uint32_t interval, uint32_t* merged_out, uint32_t* counts_out,
+                                           uint32_t* n_merged_out, int32_t n_threads)
+{
+    (void)n_threads;
+    if (interval == 0u || !n_merged_out) return hipErrorInvalidValue;
+    if (n_hits == 0u) { *n_merged_out = 0u; return hipSuccess; }
+    if (!hits || !merged_out || !counts_out) return hipErrorInvalidValue;
+    std::vector<uint64> keys(n_hits);
+    for (uint32 i = 0; i < n_hits; ++i)
+    {
+        const uint32* h = hits + 4u * uint64(i);
+        keys[i] = (uint64(h[0]) << 32) | qgram_snap(h[2] - h[1], interval);
+    }
+    qgram_merge_keys<uint64>(keys, reinterpret_cast<uint64*>(merged_out), counts_out, n_merged_out);
+    return hipSuccess;
+}

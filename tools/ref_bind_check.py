@@ -545,6 +545,38 @@ WHOLE.append(dict(name="examples/fmmap/fmmap.cu, whole TU (+ its util.h in place
                        "SparseStringSet windows into batch_banded_alignment_score<31> with the bit-vector edit-distance aligner and BestSink<int16>, cuda::reduce_by_key / cuda::reduce -- compiled as it lies and linked; "
                        "RUN here through the index and reference loaders, on the GPU box from oracle/_ref/ to its own 'aligned % reads' line",
                   tu="examples/fmmap/fmmap.cu", install="ref_fmmap", main=None, files="fmmap", run=["{index}", "{reads}"], expect="FMIndexData: loading... done", may_abort=True))
+# the query and filter part of the reference's q-gram test: its helpers (:52-126) and test_qgram_index_query (:232-393; the template header
+# of :231 restated), over a device string index, a host string index and a device set index.  The build helpers and the q-group parts
+# of that file are not taken (qgroup.h does not exist here).  Compiled and linked only.
+WHOLE.append(dict(name="nvbio-test/qgram_test.cu:52-126 + 232-393: range_size / valid_range / Stats / build_qgrams and test_qgram_index_query -- plain_view(index) as the functor of "
+                       "thrust::transform, QGramFilter<system_tag, index, const uint64*, const uint32*>::rank / locate / merge (16-bit counts) -- over QGramIndexDevice, QGramIndexHost and QGramSetIndexDevice",
+                  tu=None, install="ref_qgram_query", ranges=[("nvbio-test/qgram_test.cu", 52, 126), ("nvbio-test/qgram_test.cu", 232, 393)], wrapper=r"""
+#include <stdio.h>
+#include <stdlib.h>
+#include <nvbio/basic/timer.h>
+#include <nvbio/basic/console.h>
+#include <nvbio/basic/vector.h>
+#include <nvbio/basic/packedstream.h>
+#include <nvbio/strings/string_set.h>
+#include <nvbio/strings/seeds.h>
+#include <nvbio/qgram/qgram.h>
+#include <nvbio/qgram/filter.h>
+#include <thrust/reduce.h>
+#include <thrust/sort.h>
+#include <thrust/copy.h>
+{0}
+template <typename qgram_index_type, typename genome_string>
+{1}
+typedef PackedStream<const uint32*, uint8, 2, true> genome_type;
+void instantiate(QGramIndexDevice& d, QGramIndexHost& h, QGramSetIndexDevice& s, const uint32* d_words, const uint32* h_words, Stats& stats)
+{
+    test_qgram_index_query(d, 1000u, 100000u, 0u, genome_type(d_words), stats);
+    test_qgram_index_query(h, 1000u, 100000u, 0u, genome_type(h_words), stats);
+    test_qgram_index_query(s, 1000u, 100000u, 0u, genome_type(d_words), stats);
+}
+} // namespace nvbio
+""", main="int main() { return 0; }\n"))
+
 
 def sw_benchmark_files(tmp):
     """a 3 000-bp FASTA reference and 64 FASTQ reads cut from it, for the host part of the sw-benchmark run"""
