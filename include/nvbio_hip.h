@@ -1201,6 +1201,96 @@ int nvbio_hip_qgram_merge_host(const uint32_t* hits, uint32_t n_hits, uint32_t i
 int nvbio_hip_qgram_set_merge_host(const uint32_t* hits, uint32_t n_hits, uint32_t interval, uint32_t* merged_out, uint32_t* counts_out,
                                    uint32_t* n_merged_out, int32_t n_threads);
 
+/* ---- Byte alphabets: suffix sort and BWT of a byte text, the wavelet tree, and an FM-index over the wavelet tree of a BWT
+ * (nvbio/strings/wavelet_tree.h; fm_index<WaveletTree, ..> of nvbio/fmindex/fmindex.h).
+ * A byte text holds one symbol per byte, 1 <= symbol_size <= 8 bits of it: every symbol is read as byte & (2^symbol_size - 1), so no
+ * input byte can index outside the alphabet.
+ *
+ * nvbio_hip_suffix_sort_bytes / nvbio_hip_bwt_bytes: nvbio_hip_suffix_sort / nvbio_hip_bwt for such a text, 1 <= n <= 0xFFFFFFFE, with
+ * the same conventions (SA[0] = n, a proper prefix first, primary, ssa[k] = SA[k * sa_int] with ssa[0] = 0xFFFFFFFF), the same scratch
+ * and waits, the rounds reported by nvbio_hip_suffix_sort_last_rounds; bwt_out = the n BWT symbols, one byte each, the '$' row dropped.
+ * A null pointer, symbol_size 0 or above 8, n == 0 or above the maximum, or too little temp return hipErrorInvalidValue and launch
+ * nothing.
+ *
+ * The wavelet tree of n symbols, S = symbol_size, K = 2^S, W = ceil(n S / 32), n S <= 0xFFFFFFFF; the reference's layout bit for bit:
+ *   bits[W]     a big-endian 1-bit stream: global bit g is bit 31 - g % 32 of word g / 32, zero padded.  Level l is bits
+ *               [l n, (l + 1) n): bit S - 1 - l of the symbols after a stable sort by their top l bits.
+ *   splits[K]   a heap of internal nodes: node j of level l has index 2^l - 1 + j and covers the symbols [j K / 2^l, (j + 1) K / 2^l);
+ *               splits[node] = the text symbols smaller than the node's middle symbol; splits[K - 1] = 0.
+ *   occ[K + W]  occ[node] = the 1 bits of the stream before bit l n + (the text symbols smaller than the node's first symbol),
+ *               occ[K - 1] = 0; occ[K + w] = the 1 bits before word w.
+ * nvbio_hip_wavelet_setup is asynchronous (no wait); temp: device scratch of nvbio_hip_wavelet_setup_temp_bytes (a 256-bin histogram
+ * | n bytes of sorted symbols | rocPRIM's).
+ * nvbio_hip_wavelet_text: out[i] = the symbol at positions[i] (positions == NULL: at i); a position >= n gives 0 without a read.
+ * nvbio_hip_wavelet_rank: out[i] = the occurrences of symbols[i] & (K - 1) in [0, positions[i]]; a position in [n, 0xFFFFFFFE] counts as
+ * n - 1 (the reference's clamp), 0xFFFFFFFF gives 0.  nvbio_hip_wavelet_rank_range: the same for both ends (x, y) of n_queries ranges.
+ * n_queries <= 0xFFFFFFFF.  The queries are asynchronous.
+ *
+ * The FM-index: bwt = the tree of the n BWT symbols ('$' dropped), L2[K + 1] with L2[0] = 0 and L2[c + 1] = L2[c] + count(c)
+ * (nvbio_hip_wavelet_fm_L2 reads it off the tree), ssa as nvbio_hip_bwt_bytes writes it for sa_int (any value >= 1), primary, and
+ * length == bwt.size.
+ * nvbio_hip_wavelet_fm_match: the reference's backward search from (0, n): x = L2[c] + rank(x - 1, c) + 1, y = L2[c] + rank(y, c) while
+ * x <= y, over the pattern's symbols from the last to the first; an empty pattern gives (0, n).  A pattern symbol >= K ends the search
+ * with (1, 0): pattern symbols are the one read that is not masked (the reference tests c > K, which lets c == K through to a rank of
+ * symbol 0).  A pattern is clipped to the n_symbols the set declares.
+ * nvbio_hip_wavelet_fm_locate: positions_out[i] = SA[rows[i]] by LF steps to a sampled row; row 0 gives ssa[0] = 0xFFFFFFFF, what
+ * nvbio_hip_fm_locate gives for it; a row above n gives 0xFFFFFFFF without a read.  ssa == NULL or sa_int == 0 is refused.
+ * A null pointer, a tree or index outside the limits above (primary must be in [1, length]) return hipErrorInvalidValue and launch nothing.
+ * The host twins take host pointers and a thread count, and return the same bytes.  The query twins run their queries on n_threads
+ * threads; nvbio_hip_wavelet_setup_host and nvbio_hip_wavelet_fm_L2_host are serial whatever n_threads says (the setup is the
+ * definition itself: a stable sort of the symbols per level and a bit-by-bit fill, O(S n log n)). */
+typedef struct nvbio_hip_wavelet_tree {
+    const uint32_t* bits;       /* [W] */
+    const uint32_t* splits;     /* [K] */
+    const uint32_t* occ;        /* [K + W] */
+    uint32_t        symbol_size, size;
+} nvbio_hip_wavelet_tree;
+typedef struct nvbio_hip_byte_string_set {
+    const uint8_t*  symbols;    /* one symbol per byte */
+    uint64_t        n_symbols;
+    const uint64_t* begin;      /* [n] first symbol of each string */
+    const uint32_t* length;     /* [n], or NULL -> fixed_length */
+    uint32_t        fixed_length, _pad;
+} nvbio_hip_byte_string_set;
+typedef struct nvbio_hip_wavelet_fmindex {
+    nvbio_hip_wavelet_tree bwt; /* over the n BWT symbols, '$' dropped */
+    const uint32_t* L2;         /* [K + 1] */
+    const uint32_t* ssa;        /* may be NULL: then locate is refused */
+    uint32_t        length, primary, sa_int, _pad;
+} nvbio_hip_wavelet_fmindex;
+uint64_t nvbio_hip_suffix_sort_bytes_temp_bytes(uint64_t n);
+int nvbio_hip_suffix_sort_bytes(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t* sa_out /* [n + 1] */,
+                                void* temp, uint64_t temp_bytes, void* stream);
+uint64_t nvbio_hip_bwt_bytes_temp_bytes(uint64_t n);
+int nvbio_hip_bwt_bytes(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t sa_int, uint8_t* bwt_out /* [n] */,
+                        uint32_t* primary_out /* host */, uint32_t* ssa_out /* may be NULL */, uint32_t* sa_out /* may be NULL */,
+                        void* temp, uint64_t temp_bytes, void* stream);
+int nvbio_hip_suffix_sort_bytes_host(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t* sa_out, int32_t n_threads);
+int nvbio_hip_bwt_bytes_host(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t sa_int, uint8_t* bwt_out, uint32_t* primary_out,
+                             uint32_t* ssa_out, uint32_t* sa_out, int32_t n_threads);
+uint64_t nvbio_hip_wavelet_setup_temp_bytes(uint64_t n, uint32_t symbol_size);
+int nvbio_hip_wavelet_setup(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t* bits_out /* [W] */, uint32_t* splits_out /* [K] */,
+                            uint32_t* occ_out /* [K + W] */, void* temp, uint64_t temp_bytes, void* stream);
+int nvbio_hip_wavelet_text(const nvbio_hip_wavelet_tree* tree, const uint32_t* positions /* [n] or NULL */, uint64_t n_queries, uint8_t* out, void* stream);
+int nvbio_hip_wavelet_rank(const nvbio_hip_wavelet_tree* tree, const uint32_t* positions, const uint8_t* symbols, uint64_t n_queries, uint32_t* out, void* stream);
+int nvbio_hip_wavelet_rank_range(const nvbio_hip_wavelet_tree* tree, const uint32_t* ranges /* [2 n] */, const uint8_t* symbols, uint64_t n_queries,
+                                 uint32_t* out /* [2 n] */, void* stream);
+int nvbio_hip_wavelet_fm_L2(const nvbio_hip_wavelet_tree* tree, uint32_t* L2_out /* [K + 1] */, void* stream);
+int nvbio_hip_wavelet_fm_match(const nvbio_hip_wavelet_fmindex* fmi, const nvbio_hip_byte_string_set* patterns /* host struct, device arrays */, uint64_t n,
+                               uint32_t* ranges_out /* [2 n] */, void* stream);
+int nvbio_hip_wavelet_fm_locate(const nvbio_hip_wavelet_fmindex* fmi, const uint32_t* rows, uint64_t n_rows, uint32_t* positions_out, void* stream);
+int nvbio_hip_wavelet_setup_host(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t* bits_out, uint32_t* splits_out, uint32_t* occ_out,
+                                 int32_t n_threads);
+int nvbio_hip_wavelet_text_host(const nvbio_hip_wavelet_tree* tree, const uint32_t* positions, uint64_t n_queries, uint8_t* out, int32_t n_threads);
+int nvbio_hip_wavelet_rank_host(const nvbio_hip_wavelet_tree* tree, const uint32_t* positions, const uint8_t* symbols, uint64_t n_queries, uint32_t* out,
+                                int32_t n_threads);
+int nvbio_hip_wavelet_rank_range_host(const nvbio_hip_wavelet_tree* tree, const uint32_t* ranges, const uint8_t* symbols, uint64_t n_queries, uint32_t* out,
+                                      int32_t n_threads);
+int nvbio_hip_wavelet_fm_L2_host(const nvbio_hip_wavelet_tree* tree, uint32_t* L2_out, int32_t n_threads);
+int nvbio_hip_wavelet_fm_match_host(const nvbio_hip_wavelet_fmindex* fmi, const nvbio_hip_byte_string_set* patterns, uint64_t n, uint32_t* ranges_out,
+                                    int32_t n_threads);
+int nvbio_hip_wavelet_fm_locate_host(const nvbio_hip_wavelet_fmindex* fmi, const uint32_t* rows, uint64_t n_rows, uint32_t* positions_out, int32_t n_threads);
+
 /* Device-memory helpers for host code that has no HIP headers (the C++ host layer in
  * include/nvbio_hip/ uses them where the reference uses thrust::device_vector).
  * kind: 1 = host->device, 2 = device->host, 3 = device->device. */
@@ -1269,7 +1359,7 @@ void nvbio_hip_comm_set_transport(const nvbio_hip_comm_transport* transport);
 
 /* Test switches.  A few named integers select alternative executions of the same results, for the parity suite to cover both
  * (NVBIO_HIP_FORCE_32BIT, NVBIO_HIP_NO_STAGING, NVBIO_HIP_FULL_GENERIC, NVBIO_HIP_FULL_SINGLE_JOB, NVBIO_HIP_FULL_ROWS, NVBIO_HIP_ED_SWEEP,
- * NVBIO_HIP_SELECT_LANES, NVBIO_HIP_TRACEBACK_LANES, NVBIO_HIP_BANDED_PAIR, NVBIO_HIP_PAIR_ROW, NVBIO_HIP_PAIR_CONST, NVBIO_HIP_PAIR_SUB).  Each is seeded ONCE per process from the environment variable of the same name and
+ * NVBIO_HIP_SELECT_LANES, NVBIO_HIP_TRACEBACK_LANES, NVBIO_HIP_BANDED_PAIR, NVBIO_HIP_PAIR_ROW, NVBIO_HIP_PAIR_CONST, NVBIO_HIP_PAIR_SUB, NVBIO_HIP_WAVELET_LANES).  Each is seeded ONCE per process from the environment variable of the same name and
  * changed afterwards only through nvbio_hip_set_test_switch (atomic; safe while other threads are inside library calls -- a call in flight
  * uses the value it read when it started).  0 = the default execution.  Production code leaves them alone. */
 int nvbio_hip_set_test_switch(const char* name, int value);     /* hipErrorInvalidValue for an unknown name */

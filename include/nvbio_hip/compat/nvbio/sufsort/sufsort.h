@@ -22,7 +22,9 @@
 //
 // `string` is a device-side iterator over a 2-bit alphabet.  A PackedStream over a word pointer that starts on a word boundary goes to
 // nvbio_hip_suffix_sort / nvbio_hip_bwt (include/nvbio_hip.h) in place; any other 2-bit iterator is packed into
-// big-endian words first, then takes the same call.  Wider alphabets throw.  A string set is a ConcatenatedStringSet over a 2-bit
+// big-endian words first, then takes the same call.  An iterator over any other alphabet of up to 8 bits (an 8-bit PackedVector of
+// proteins, plain bytes) is unpacked to one symbol per byte and goes to nvbio_hip_suffix_sort_bytes / nvbio_hip_bwt_bytes; wider symbols
+// throw.  A string set is a ConcatenatedStringSet over a 2-bit
 // PackedStream on a word pointer with device offsets; it goes to nvbio_hip_set_suffix_sort / nvbio_hip_set_bwt in place, at whatever
 // symbol its stream starts.  blockwise_suffix_sort, large_bwt (sets that do not fit the device), the file handlers and 4-bit sets are
 // not provided.  Needs a translation unit compiled by hipcc and linked with libnvbio_hip.
@@ -172,6 +174,94 @@ inline void check_length(const uint64 n)
     if (n == 0u || n > 0xFFFFFFFEull) throw std::runtime_error("nvbio::cuda sufsort: the string must hold between 1 and 2^32 - 2 symbols");
 }
 
+/// ---- alphabets other than 2-bit, up to 8 bits a symbol: the string as one symbol per byte, for the `_bytes` entries ----
+
+template <typename string_type>
+__global__ void to_bytes_kernel(const uint64 n, const string_type string, uint8* bytes)
+{
+    const uint64 i = uint64(blockIdx.x) * 256u + threadIdx.x;
+    if (i < n) bytes[i] = uint8(string[i]);
+}
+
+/// how an output iterator shares words: a PackedStream holds `per` symbols a word and starts `phase` symbols into one; anything else
+/// owns each element
+template <typename It> struct output_words { static uint32 per(const It&) { return 1u; } static uint32 phase(const It&) { return 0u; } };
+template <typename I, typename S, uint32 B, bool E, typename X>
+struct output_words< PackedStream<I, S, B, E, X> >
+{
+    typedef PackedStream<I, S, B, E, X> stream;
+    static uint32 per(const stream&) { return stream::SYMBOLS_PER_WORD; }
+    static uint32 phase(const stream& s) { return uint32(uint64(s.index()) % stream::SYMBOLS_PER_WORD); }
+};
+
+/// output[i] = in[i]; lane t owns the symbols whose position from the output's word boundary is in [per t, per t + per), so no two
+/// lanes write one word of a packed output
+template <typename output_iterator>
+__global__ void from_bytes_kernel(const uint64 n, const uint8* in, output_iterator output, const uint32 phase, const uint32 per, const uint64 n_lanes)
+{
+    const uint64 t = uint64(blockIdx.x) * 256u + threadIdx.x;
+    if (t >= n_lanes) return;
+    for (uint32 q = 0; q < per; ++q)
+    {
+        const uint64 at = t * per + q;
+        if (at < phase) continue;
+        const uint64 i = at - phase;
+        if (i < n) output[i] = in[i];
+    }
+}
+
+template <typename string_type>
+struct byte_text
+{
+    static const uint32 SYMBOL_SIZE = stream_traits<string_type>::SYMBOL_SIZE;
+    byte_text(const uint64 n, const string_type& string) : bytes(n)
+    {
+        if (SYMBOL_SIZE < 1u || SYMBOL_SIZE > 8u) throw std::runtime_error("nvbio::cuda sufsort: only alphabets of up to 8 bits a symbol are supported");
+        hipLaunchKernelGGL((to_bytes_kernel<string_type>), dim3(uint32((n + 255u) / 256u)), dim3(256), 0, 0, n, string, bytes.template as<uint8>());
+        check(hipGetLastError(), "to_bytes_kernel");
+    }
+    scratch bytes;
+};
+
+template <typename string_type, typename output_iterator>
+void suffix_sort_bytes(const uint64 n, const string_type& string, output_iterator output)
+{
+    byte_text<string_type> text(n, string);
+    const uint64 tb = nvbio_hip_suffix_sort_bytes_temp_bytes(n);
+    scratch temp(tb);
+    if (uint32* direct = plain_words<output_iterator>::get(output))
+    {
+        check(nvbio_hip_suffix_sort_bytes(text.bytes.template as<uint8>(), text.SYMBOL_SIZE, n, direct, temp.ptr, tb, nullptr), "nvbio_hip_suffix_sort_bytes");
+        return;
+    }
+    scratch sa((n + 1u) * 4u);
+    check(nvbio_hip_suffix_sort_bytes(text.bytes.template as<uint8>(), text.SYMBOL_SIZE, n, sa.as<uint32>(), temp.ptr, tb, nullptr), "nvbio_hip_suffix_sort_bytes");
+    hipLaunchKernelGGL((copy_kernel<output_iterator>), dim3(uint32((n + 256u) / 256u)), dim3(256), 0, 0, n + 1u, sa.as<uint32>(), output);
+    check(hipGetLastError(), "copy_kernel");
+    check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+}
+
+/// the BWT symbols into `output` (NULL: the primary alone); returns the primary
+template <typename string_type, typename output_iterator>
+uint32 bwt_bytes(const uint64 n, const string_type& string, output_iterator* output)
+{
+    byte_text<string_type> text(n, string);
+    const uint64 tb = nvbio_hip_bwt_bytes_temp_bytes(n);
+    scratch temp(tb);
+    scratch out(n);
+    uint32 primary = 0;
+    check(nvbio_hip_bwt_bytes(text.bytes.template as<uint8>(), text.SYMBOL_SIZE, n, 0u, out.as<uint8>(), &primary, nullptr, nullptr, temp.ptr, tb, nullptr), "nvbio_hip_bwt_bytes");
+    if (output)
+    {
+        const uint32 per = output_words<output_iterator>::per(*output), phase = output_words<output_iterator>::phase(*output);
+        const uint64 n_lanes = (n + phase + per - 1u) / per;
+        hipLaunchKernelGGL((from_bytes_kernel<output_iterator>), dim3(uint32((n_lanes + 255u) / 256u)), dim3(256), 0, 0, n, out.as<uint8>(), *output, phase, per, n_lanes);
+        check(hipGetLastError(), "from_bytes_kernel");
+        check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    }
+    return primary;
+}
+
 /// begin[s] = first + offsets[s] and length[s] of every string of a concatenated set, as the C-ABI takes them; ends[0 .. 1] = the
 /// first and the last offset
 template <typename offset_iterator>
@@ -279,6 +369,7 @@ void suffix_sort(
     (void)params;
     const uint64 n = string_len;
     sufsort::check_length(n);
+    if constexpr (stream_traits<string_type>::SYMBOL_SIZE != 2u) { sufsort::suffix_sort_bytes(n, string, output); return; }
     sufsort::packed_text<string_type> text(n, string);
     const uint64 tb = nvbio_hip_suffix_sort_temp_bytes(n);
     sufsort::scratch temp(tb);
@@ -305,6 +396,7 @@ typename string_type::index_type bwt(
     (void)params;
     const uint64 n = string_len;
     sufsort::check_length(n);
+    if constexpr (stream_traits<string_type>::SYMBOL_SIZE != 2u) return typename string_type::index_type(sufsort::bwt_bytes(n, string, &output));
     sufsort::packed_text<string_type> text(n, string);
     const uint64 tb = nvbio_hip_bwt_temp_bytes(n);
     sufsort::scratch temp(tb);
@@ -327,6 +419,7 @@ typename string_type::index_type find_primary(
 {
     const uint64 n = string_len;
     sufsort::check_length(n);
+    if constexpr (stream_traits<string_type>::SYMBOL_SIZE != 2u) return typename string_type::index_type(sufsort::bwt_bytes(n, string, (uint8**)nullptr));
     sufsort::packed_text<string_type> text(n, string);
     const uint64 tb = nvbio_hip_bwt_temp_bytes(n);
     sufsort::scratch temp(tb);

@@ -6,6 +6,7 @@
 //   suffix_sort(text, sa)        sa: n + 1 rows, sa[0] = n, a suffix that is a proper prefix of another first
 //   bwt(text, sa_int, out)       the BWT with the '$' row dropped (big-endian words, what nvbio_hip_build_bwt_occ takes), the primary,
 //                                and on request the sampled and the whole suffix array
+//   suffix_sort_bytes / bwt_bytes  the same for a byte text of 1 to 8 bits a symbol (nvbio_hip_suffix_sort_bytes / nvbio_hip_bwt_bytes)
 //
 // and of the same module's string-set front door, thin callers of nvbio_hip_set_suffix_sort / nvbio_hip_set_bwt:
 //
@@ -76,6 +77,38 @@ inline void bwt(const PackedTextView<BE>& text, const uint32 sa_int, BWTResult& 
 {
     device_vector<uint8> temp;
     bwt(text, sa_int, out, temp, want_ssa, want_sa, stream);
+}
+
+/// what bwt_bytes() returns
+struct ByteBWTResult
+{
+    ByteBWTResult() : primary(0) {}
+    uint32                 primary;        ///< the row whose suffix is 0
+    device_vector<uint8>   bwt;            ///< n symbols, one byte each, the '$' row dropped
+    device_vector<uint32>  ssa;            ///< ceil((n + 1) / sa_int) samples, ssa[0] = 0xFFFFFFFF (empty unless asked for)
+    device_vector<uint32>  sa;             ///< n + 1 rows (empty unless asked for)
+};
+
+/// suffix_sort for a byte text in device memory: one symbol per byte, of which the low symbol_size (1 to 8) bits are read
+inline void suffix_sort_bytes(const uint8* symbols, const uint32 symbol_size, const uint64 n, device_vector<uint32>& sa, device_vector<uint8>& temp, void* stream = nullptr)
+{
+    const uint64 tb = nvbio_hip_suffix_sort_bytes_temp_bytes(n);
+    if (temp.size() < tb) temp.resize(tb);
+    sa.resize(n + 1u);
+    hip_check(nvbio_hip_suffix_sort_bytes(symbols, symbol_size, n, sa.data(), temp.data(), temp.size(), stream), "nvbio_hip_suffix_sort_bytes");
+}
+
+/// bwt for a byte text: the BWT symbols, the primary and (want_ssa) the sampled, (want_sa) the whole suffix array
+inline void bwt_bytes(const uint8* symbols, const uint32 symbol_size, const uint64 n, const uint32 sa_int, ByteBWTResult& out, device_vector<uint8>& temp,
+                      const bool want_ssa = true, const bool want_sa = false, void* stream = nullptr)
+{
+    const uint64 tb = nvbio_hip_bwt_bytes_temp_bytes(n);
+    if (temp.size() < tb) temp.resize(tb);
+    out.bwt.resize(n);
+    if (want_ssa) out.ssa.resize(sa_int ? (n + sa_int) / sa_int : 0u);
+    if (want_sa)  out.sa.resize(n + 1u);
+    hip_check(nvbio_hip_bwt_bytes(symbols, symbol_size, n, sa_int, out.bwt.data(), &out.primary, want_ssa ? out.ssa.data() : nullptr,
+                                  want_sa ? out.sa.data() : nullptr, temp.data(), temp.size(), stream), "nvbio_hip_bwt_bytes");
 }
 
 /// the slots of a 2-bit string set, the n_suffixes of the calls below: the sum of length + 1 (one copy of the lengths to the host, unless

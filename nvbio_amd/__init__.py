@@ -19,5 +19,7 @@ from .fmindex import FMIndexDevice, FMIndexFilter, MEMFilter, rank, rank4, rank_
     locate_ssa_iterator, lookup_ssa_iterator, extend_forward, extend_backwards, build_bwt_occ  # noqa: F401
 from .sufsort import suffix_sort, bwt, build_fm_index, set_suffix_sort, set_bwt  # noqa: F401
 from .qgram import generate_qgrams, QGramIndex, QGramSetIndex, QGramFilter  # noqa: F401
+from .wavelet import WaveletTree, WaveletFMIndex, ByteStringSet, suffix_sort_bytes, bwt_bytes  # noqa: F401
+from . import alphabet  # noqa: F401
 from .mapping import MappingParams, map_exact, map_seeds, unpack_seed_hits  # noqa: F401
 from .reduce import BestAlignments, score_reduce, score_reduce_paired, mapq, mapq_paired, opposite_mate_windows  # noqa: F401

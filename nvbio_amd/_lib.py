@@ -43,12 +43,23 @@ SYMBOLS = [
     "nvbio_hip_qgram_generate_host", "nvbio_hip_qgram_set_generate_host", "nvbio_hip_qgram_index_build_host", "nvbio_hip_qgram_set_count_seeds_host",
     "nvbio_hip_qgram_set_index_build_host", "nvbio_hip_qgram_range_host", "nvbio_hip_qgram_rank_host", "nvbio_hip_qgram_locate_host",
     "nvbio_hip_qgram_set_locate_host", "nvbio_hip_qgram_merge_host", "nvbio_hip_qgram_set_merge_host",
+    "nvbio_hip_suffix_sort_bytes_temp_bytes", "nvbio_hip_suffix_sort_bytes", "nvbio_hip_bwt_bytes_temp_bytes", "nvbio_hip_bwt_bytes",
+    "nvbio_hip_suffix_sort_bytes_host", "nvbio_hip_bwt_bytes_host",
+    "nvbio_hip_wavelet_setup_temp_bytes", "nvbio_hip_wavelet_setup", "nvbio_hip_wavelet_text", "nvbio_hip_wavelet_rank", "nvbio_hip_wavelet_rank_range",
+    "nvbio_hip_wavelet_fm_match", "nvbio_hip_wavelet_fm_locate",
+    "nvbio_hip_wavelet_setup_host", "nvbio_hip_wavelet_text_host", "nvbio_hip_wavelet_rank_host", "nvbio_hip_wavelet_rank_range_host",
+    "nvbio_hip_wavelet_fm_match_host", "nvbio_hip_wavelet_fm_locate_host",
     "nvbio_hip_device_malloc", "nvbio_hip_device_free", "nvbio_hip_device_free_ordered", "nvbio_hip_device_free_after", "nvbio_hip_device_trim", "nvbio_hip_device_mem_info", "nvbio_hip_memcpy", "nvbio_hip_memset",
     "nvbio_hip_stream_synchronize", "nvbio_hip_stream_query", "nvbio_hip_host_malloc", "nvbio_hip_host_free", "nvbio_hip_stream_create", "nvbio_hip_stream_destroy",
     "nvbio_hip_comm_available", "nvbio_hip_device_count", "nvbio_hip_set_device", "nvbio_hip_get_device", "nvbio_hip_comm_unique_id", "nvbio_hip_comm_init_rank",
     "nvbio_hip_comm_init_all", "nvbio_hip_comm_destroy", "nvbio_hip_comm_rank", "nvbio_hip_gather_records", "nvbio_hip_comm_abort", "nvbio_hip_comm_set_transport",
     "nvbio_hip_abi_version", "nvbio_hip_arch", "nvbio_hip_last_kernel", "nvbio_hip_last_kernel_detail", "nvbio_hip_last_kernel_cell", "nvbio_hip_last_kernel_frame", "nvbio_hip_last_kernel_row", "nvbio_hip_last_kernel_const", "nvbio_hip_last_kernel_sub", "nvbio_hip_last_kernel_subread", "nvbio_hip_last_kernel_fetch", "nvbio_hip_set_test_switch", "nvbio_hip_get_test_switch", "nvbio_hip_test_switch_name",
 ]
+
+
+# declared in include/nvbio_hip.h under the array's own name, capital included: tests/test_abi.py's pattern reads lower-case names only, so
+# they are listed apart; the loader checks them with the rest and tests/test_wavelet_host.py compares this list with the header
+CAPITAL_SYMBOLS = ["nvbio_hip_wavelet_fm_L2", "nvbio_hip_wavelet_fm_L2_host"]
 
 
 class PeParamsStruct(C.Structure):       # nvbio_hip_pe_params
@@ -64,6 +75,20 @@ class StringSetStruct(C.Structure):      # nvbio_hip_string_set
 class QGramIndexStruct(C.Structure):     # nvbio_hip_qgram_index
     _fields_ = [("qgrams", C.c_void_p), ("slots", C.c_void_p), ("index", C.c_void_p), ("lut", C.c_void_p),
                 ("q", C.c_uint32), ("ql", C.c_uint32), ("n_unique", C.c_uint32), ("n_qgrams", C.c_uint32)]
+
+
+class WaveletTreeStruct(C.Structure):    # nvbio_hip_wavelet_tree
+    _fields_ = [("bits", C.c_void_p), ("splits", C.c_void_p), ("occ", C.c_void_p), ("symbol_size", C.c_uint32), ("size", C.c_uint32)]
+
+
+class ByteStringSetStruct(C.Structure):  # nvbio_hip_byte_string_set
+    _fields_ = [("symbols", C.c_void_p), ("n_symbols", C.c_uint64), ("begin", C.c_void_p), ("length", C.c_void_p),
+                ("fixed_length", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class WaveletFMIndexStruct(C.Structure):  # nvbio_hip_wavelet_fmindex
+    _fields_ = [("bwt", WaveletTreeStruct), ("L2", C.c_void_p), ("ssa", C.c_void_p),
+                ("length", C.c_uint32), ("primary", C.c_uint32), ("sa_int", C.c_uint32), ("_pad", C.c_uint32)]
 
 
 class GotohSchemeStruct(C.Structure):    # nvbio_hip_gotoh_scheme
@@ -108,7 +133,7 @@ def lib():
             found = None
         if found != ABI_VERSION:
             raise RuntimeError("nvbio_amd: lib/libnvbio_hip.so has ABI version %s, this package needs %d -- rebuild it (python -m nvbio_amd.build)" % (found, ABI_VERSION))
-        for s in SYMBOLS:
+        for s in SYMBOLS + CAPITAL_SYMBOLS:
             getattr(L, s)   # AttributeError if the library does not export the ABI
         vp, u32, u64, i32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
         P = C.POINTER
@@ -292,6 +317,31 @@ def lib():
         L.nvbio_hip_qgram_set_locate_host.argtypes = [QI, u32, vp, vp, vp, u64, u64, vp, i32]
         L.nvbio_hip_qgram_merge_host.argtypes = [vp, u32, u32, vp, vp, P(u32), i32]
         L.nvbio_hip_qgram_set_merge_host.argtypes = [vp, u32, u32, vp, vp, P(u32), i32]
+        WT, WF, BS = P(WaveletTreeStruct), P(WaveletFMIndexStruct), P(ByteStringSetStruct)
+        L.nvbio_hip_suffix_sort_bytes_temp_bytes.argtypes = [u64]
+        L.nvbio_hip_suffix_sort_bytes_temp_bytes.restype = u64
+        L.nvbio_hip_suffix_sort_bytes.argtypes = [vp, u32, u64, vp, vp, u64, vp]
+        L.nvbio_hip_bwt_bytes_temp_bytes.argtypes = [u64]
+        L.nvbio_hip_bwt_bytes_temp_bytes.restype = u64
+        L.nvbio_hip_bwt_bytes.argtypes = [vp, u32, u64, u32, vp, P(u32), vp, vp, vp, u64, vp]
+        L.nvbio_hip_suffix_sort_bytes_host.argtypes = [vp, u32, u64, vp, i32]
+        L.nvbio_hip_bwt_bytes_host.argtypes = [vp, u32, u64, u32, vp, P(u32), vp, vp, i32]
+        L.nvbio_hip_wavelet_setup_temp_bytes.argtypes = [u64, u32]
+        L.nvbio_hip_wavelet_setup_temp_bytes.restype = u64
+        L.nvbio_hip_wavelet_setup.argtypes = [vp, u32, u64, vp, vp, vp, vp, u64, vp]
+        L.nvbio_hip_wavelet_text.argtypes = [WT, vp, u64, vp, vp]
+        L.nvbio_hip_wavelet_rank.argtypes = [WT, vp, vp, u64, vp, vp]
+        L.nvbio_hip_wavelet_rank_range.argtypes = [WT, vp, vp, u64, vp, vp]
+        L.nvbio_hip_wavelet_fm_match.argtypes = [WF, BS, u64, vp, vp]
+        L.nvbio_hip_wavelet_fm_locate.argtypes = [WF, vp, u64, vp, vp]
+        L.nvbio_hip_wavelet_setup_host.argtypes = [vp, u32, u64, vp, vp, vp, i32]
+        L.nvbio_hip_wavelet_text_host.argtypes = [WT, vp, u64, vp, i32]
+        L.nvbio_hip_wavelet_rank_host.argtypes = [WT, vp, vp, u64, vp, i32]
+        L.nvbio_hip_wavelet_rank_range_host.argtypes = [WT, vp, vp, u64, vp, i32]
+        L.nvbio_hip_wavelet_fm_match_host.argtypes = [WF, BS, u64, vp, i32]
+        L.nvbio_hip_wavelet_fm_locate_host.argtypes = [WF, vp, u64, vp, i32]
+        L.nvbio_hip_wavelet_fm_L2.argtypes = [WT, vp, vp]
+        L.nvbio_hip_wavelet_fm_L2_host.argtypes = [WT, vp, i32]
         L.nvbio_hip_comm_unique_id.argtypes = [vp]
         L.nvbio_hip_comm_init_rank.argtypes = [P(vp), C.c_int, C.c_int, vp]
         L.nvbio_hip_comm_init_all.argtypes = [vp, C.c_int, vp]

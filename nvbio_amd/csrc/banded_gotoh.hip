@@ -725,7 +725,8 @@ namespace nvb {
 static std::atomic<int> g_switch[SW_COUNT];
 static const char* const g_switch_name[SW_COUNT] = { "NVBIO_HIP_FORCE_32BIT", "NVBIO_HIP_NO_STAGING", "NVBIO_HIP_FULL_GENERIC", "NVBIO_HIP_ED_SWEEP",
                                                      "NVBIO_HIP_FULL_SINGLE_JOB", "NVBIO_HIP_FULL_ROWS", "NVBIO_HIP_TRACEBACK_LANES", "NVBIO_HIP_SELECT_LANES",
-                                                     "NVBIO_HIP_BANDED_PAIR", "NVBIO_HIP_PAIR_ROW", "NVBIO_HIP_PAIR_CONST", "NVBIO_HIP_PAIR_SUB" };
+                                                     "NVBIO_HIP_BANDED_PAIR", "NVBIO_HIP_PAIR_ROW", "NVBIO_HIP_PAIR_CONST", "NVBIO_HIP_PAIR_SUB",
+                                                     "NVBIO_HIP_WAVELET_LANES" };
 static void seed_switches()
 {
     static std::once_flag once;

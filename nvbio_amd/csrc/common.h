@@ -27,7 +27,7 @@ extern thread_local PairLaunch g_last_pair;
 // Test switches (include/nvbio_hip.h, "Test switches"): alternative executions of the same results.  Each is an atomic int, seeded ONCE
 // from the environment variable of the same name (std::call_once) and changed afterwards only through nvbio_hip_set_test_switch --
 // no getenv on the launch paths, which run on several driver threads at a time.
-enum TestSwitch { SW_FORCE_32BIT = 0, SW_NO_STAGING, SW_FULL_GENERIC, SW_ED_SWEEP, SW_FULL_SINGLE_JOB, SW_FULL_ROWS, SW_TRACEBACK_LANES, SW_SELECT_LANES, SW_BANDED_PAIR, SW_PAIR_ROW, SW_PAIR_CONST, SW_PAIR_SUB, SW_COUNT };
+enum TestSwitch { SW_FORCE_32BIT = 0, SW_NO_STAGING, SW_FULL_GENERIC, SW_ED_SWEEP, SW_FULL_SINGLE_JOB, SW_FULL_ROWS, SW_TRACEBACK_LANES, SW_SELECT_LANES, SW_BANDED_PAIR, SW_PAIR_ROW, SW_PAIR_CONST, SW_PAIR_SUB, SW_WAVELET_LANES, SW_COUNT };
 int test_switch(TestSwitch which);       // the switch's integer value; 0 = default execution
 
 // ---------------------------------------------------------------------------

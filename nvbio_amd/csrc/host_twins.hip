@@ -403,15 +403,17 @@ inline uint32 text_symbol(const uint32* words, const uint32 be, const uint64 i)
     return (words[i >> 4] >> (be ? 30u - 2u * k : 2u * k)) & 3u;
 }
 
-int suffix_sort_host(const uint32* words, const uint32 be, const uint64 n, uint32* sa, const int threads)
+/// sym(i): symbol i of the text
+template <typename Sym>
+int suffix_sort_host_of(const Sym sym, const uint64 n, uint32* sa, const int threads)
 {
-    // rank 0 = past the end, so a suffix that is a prefix of another sorts first; symbols are 1..4 in the first round
+    // rank 0 = past the end, so a suffix that is a prefix of another sorts first; symbols are 1.. in the first round
     std::vector<uint32> rank(n), next(n);
     std::vector<uint64> key(n);
     uint32* rows = sa + 1;
     sa[0] = uint32(n);
     #pragma omp parallel for schedule(static) num_threads(threads)
-    for (int64 i = 0; i < int64(n); ++i) { rows[i] = uint32(i); rank[i] = text_symbol(words, be, uint64(i)) + 1u; }
+    for (int64 i = 0; i < int64(n); ++i) { rows[i] = uint32(i); rank[i] = uint32(sym(uint64(i))) + 1u; }
     for (uint64 h = 1;; h *= 2u)
     {
         #pragma omp parallel for schedule(static) num_threads(threads)
@@ -427,6 +429,11 @@ int suffix_sort_host(const uint32* words, const uint32 be, const uint64 n, uint3
         rank.swap(next);
         if (groups == n) return hipSuccess;
     }
+}
+
+int suffix_sort_host(const uint32* words, const uint32 be, const uint64 n, uint32* sa, const int threads)
+{
+    return suffix_sort_host_of([=](const uint64 i) { return text_symbol(words, be, i); }, n, sa, threads);
 }
 
 inline int sufsort_args(const uint32* words, const uint32 bits, const uint64 n)
@@ -864,5 +871,249 @@ NVB_API int nvbio_hip_qgram_set_merge_host(const uint32_t* hits, uint32_t n_hits
         keys[i] = (uint64(h[0]) << 32) | qgram_snap(h[2] - h[1], interval);
     }
     qgram_merge_keys<uint64>(keys, reinterpret_cast<uint64*>(merged_out), counts_out, n_merged_out);
+    return hipSuccess;
+}
+
+// ---- byte alphabets (sufsort.hip's `_bytes` entries, wavelet.hip): the suffix sort above over masked bytes, the tree by its definition
+// (a stable sort by the top l bits for every level, the node table by counting bits of the finished stream), and the walks in the
+// reference's terms (wavelet_tree_inl.h:339-497: inclusive positions, the clamp to the level's end, 0 at an empty node) ----
+namespace {
+
+inline int host_threads(const int32 n_threads)
+{
+#if defined(_OPENMP)
+    return n_threads > 0 ? n_threads : omp_get_max_threads();
+#else
+    (void)n_threads;
+    return 1;
+#endif
+}
+
+inline bool bytes_args_ok(const uint8* symbols, const uint32 S, const uint64 n) { return symbols && S >= 1u && S <= 8u && n >= 1u && n <= 0xFFFFFFFEull; }
+inline bool wavelet_size_ok(const uint64 n, const uint32 S) { return S >= 1u && S <= 8u && n >= 1u && n * S <= 0xFFFFFFFFull; }
+inline bool wavelet_ok(const nvbio_hip_wavelet_tree* t) { return t && t->bits && t->splits && t->occ && wavelet_size_ok(t->size, t->symbol_size); }
+inline bool wavelet_fm_ok(const nvbio_hip_wavelet_fmindex* f)
+{
+    return f && f->L2 && wavelet_ok(&f->bwt) && f->length == f->bwt.size && f->primary >= 1u && f->primary <= f->length;
+}
+
+inline uint32 wt_bit(const uint32* bits, const uint64 g) { return (bits[g >> 5] >> (31u - uint32(g & 31u))) & 1u; }
+
+/// bits equal to b among the first `count` (>= 1) bits of a node of level l that starts `begin` bits into its level; `before` = occ[node].
+/// The last bit looked at is clamped to the level's end, as the reference's node rank does.
+inline uint32 wt_count_in_node(const nvbio_hip_wavelet_tree& t, const uint32 l, const uint32 before, const uint32 begin, const uint32 count, const uint32 b)
+{
+    const uint32 K = 1u << t.symbol_size;
+    const uint32 first = l * t.size + begin;                                    // the node's first bit in the stream
+    const uint32 last = std::min(first + count - 1u, (l + 1u) * t.size - 1u);   // inclusive
+    const uint32 w = last >> 5, keep = (last & 31u) + 1u;                       // `keep` leading bits of word w belong to the prefix
+    const uint32 ones_to_last = t.occ[K + w] + uint32(__builtin_popcount(t.bits[w] >> (32u - keep)));
+    const uint32 ones = ones_to_last - before;
+    return b ? ones : (last + 1u - first) - ones;
+}
+
+/// occurrences of symbol c in [0, i]; i = 0xFFFFFFFF gives 0, i >= size counts the whole text
+inline uint32 wt_rank_host(const nvbio_hip_wavelet_tree& t, const uint32 i, const uint32 c)
+{
+    const uint32 S = t.symbol_size;
+    uint32 node = 0u, begin = 0u, end = t.size, count = i + 1u;                 // the node's symbols are [begin, end) of the sorted text
+    for (uint32 l = 0; l < S; ++l)
+    {
+        if (begin == end) return 0u;                                            // an empty node
+        const uint32 b = (c >> (S - 1u - l)) & 1u;
+        if (count) count = wt_count_in_node(t, l, t.occ[node], begin, count, b);
+        const uint32 middle = t.splits[node];
+        if (b) begin = middle; else end = middle;
+        node = 2u * node + 1u + b;
+    }
+    return count;
+}
+
+/// the symbol at i < size; r_out = its occurrences before i
+inline uint32 wt_text_host(const nvbio_hip_wavelet_tree& t, const uint32 i, uint32* r_out = nullptr)
+{
+    const uint32 S = t.symbol_size;
+    uint32 node = 0u, begin = 0u, at = i, c = 0u;                               // `at`: the symbol's place inside its node
+    for (uint32 l = 0; l < S; ++l)
+    {
+        const uint32 b = wt_bit(t.bits, uint64(l) * t.size + begin + at);
+        c = (c << 1) | b;
+        if (at) at = wt_count_in_node(t, l, t.occ[node], begin, at, b);         // the equal bits before it
+        if (b) begin = t.splits[node];
+        node = 2u * node + 1u + b;
+    }
+    if (r_out) *r_out = at;
+    return c;
+}
+
+/// rank(fmi, k, c) of fmindex_inl.h:36-57 over the tree
+inline uint32 wt_fm_rank_host(const nvbio_hip_wavelet_fmindex& f, uint32 k, const uint32 c)
+{
+    if (k == 0xFFFFFFFFu) return 0u;
+    if (k == f.length) return f.L2[c + 1u] - f.L2[c];
+    if (k >= f.primary) --k;
+    return wt_rank_host(f.bwt, k, c);
+}
+
+} // anonymous namespace
+
+NVB_API int nvbio_hip_suffix_sort_bytes_host(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t* sa_out, int32_t n_threads)
+{
+    if (!bytes_args_ok(symbols, symbol_size, n) || !sa_out) return hipErrorInvalidValue;
+    const uint32 mask = (1u << symbol_size) - 1u;
+    return suffix_sort_host_of([=](const uint64 i) { return uint32(symbols[i]) & mask; }, n, sa_out, host_threads(n_threads));
+}
+
+NVB_API int nvbio_hip_bwt_bytes_host(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t sa_int, uint8_t* bwt_out, uint32_t* primary_out,
+                                     uint32_t* ssa_out, uint32_t* sa_out, int32_t n_threads)
+{
+    if (!bytes_args_ok(symbols, symbol_size, n)) return hipErrorInvalidValue;
+    if (!bwt_out || !primary_out || (ssa_out && sa_int == 0u)) return hipErrorInvalidValue;
+    std::vector<uint32> own;
+    if (!sa_out) { own.resize(n + 1u); sa_out = own.data(); }
+    const uint32 mask = (1u << symbol_size) - 1u;
+    if (int e = suffix_sort_host_of([=](const uint64 i) { return uint32(symbols[i]) & mask; }, n, sa_out, host_threads(n_threads))) return e;
+    uint64 primary = 0;
+    for (uint64 r = 0; r <= n; ++r) if (sa_out[r] == 0u) { primary = r; break; }
+    *primary_out = uint32(primary);
+    for (uint64 j = 0; j < n; ++j) bwt_out[j] = uint8(symbols[sa_out[j + (j >= primary ? 1u : 0u)] - 1u] & mask);
+    if (ssa_out)
+    {
+        const uint64 n_ssa = (n + sa_int) / sa_int;
+        for (uint64 k = 0; k < n_ssa; ++k) ssa_out[k] = k ? sa_out[k * sa_int] : 0xFFFFFFFFu;
+    }
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_wavelet_setup_host(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t* bits_out, uint32_t* splits_out, uint32_t* occ_out,
+                                         int32_t n_threads)
+{
+    (void)n_threads;
+    if (!symbols || !bits_out || !splits_out || !occ_out || !wavelet_size_ok(n, symbol_size)) return hipErrorInvalidValue;
+    const uint32 S = symbol_size, K = 1u << S;
+    const uint64 W = (n * S + 31u) / 32u;
+    std::vector<uint8> cur(n);
+    for (uint64 i = 0; i < n; ++i) cur[i] = uint8(symbols[i] & (K - 1u));
+    std::fill(bits_out, bits_out + W, 0u);
+    for (uint32 l = 0; l < S; ++l)
+    {
+        for (uint64 i = 0; i < n; ++i)
+            if ((cur[i] >> (S - 1u - l)) & 1u) { const uint64 g = uint64(l) * n + i; bits_out[g >> 5] |= 1u << (31u - uint32(g & 31u)); }
+        const uint32 sh = S - 1u - l;                                   // the next level's order: by the top l + 1 bits
+        std::stable_sort(cur.begin(), cur.end(), [sh](const uint8 a, const uint8 b) { return (a >> sh) < (b >> sh); });
+    }
+    uint32 sum = 0u;
+    for (uint64 w = 0; w < W; ++w) { occ_out[K + w] = sum; sum += uint32(__builtin_popcount(bits_out[w])); }
+    // cur is the sorted text by now: C(s) = the symbols smaller than s
+    const auto C = [&](const uint32 s) { return uint32(std::lower_bound(cur.begin(), cur.end(), s, [](const uint8 a, const uint32 v) { return uint32(a) < v; }) - cur.begin()); };
+    const auto ones_before = [&](const uint64 g) { uint32 c = (g >> 5) < W ? occ_out[K + (g >> 5)] : sum; for (uint64 k = g & ~31ull; k < g; ++k) c += wt_bit(bits_out, k); return c; };
+    for (uint32 l = 0; l < S; ++l)
+        for (uint32 j = 0; j < (1u << l); ++j)
+        {
+            const uint32 node = (1u << l) - 1u + j, first = j * (K >> l), mid = first + (K >> (l + 1u));
+            splits_out[node] = C(mid);
+            occ_out[node] = ones_before(uint64(l) * n + C(first));
+        }
+    splits_out[K - 1u] = 0u;
+    occ_out[K - 1u] = 0u;
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_wavelet_text_host(const nvbio_hip_wavelet_tree* tree, const uint32_t* positions, uint64_t n_queries, uint8_t* out, int32_t n_threads)
+{
+    if (!wavelet_ok(tree) || n_queries > 0xFFFFFFFFull || (n_queries && !out)) return hipErrorInvalidValue;
+    const int threads = host_threads(n_threads);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 k = 0; k < int64(n_queries); ++k)
+    {
+        const uint64 p = positions ? uint64(positions[k]) : uint64(k);
+        out[k] = p < tree->size ? uint8(wt_text_host(*tree, uint32(p))) : uint8(0);
+    }
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_wavelet_rank_host(const nvbio_hip_wavelet_tree* tree, const uint32_t* positions, const uint8_t* symbols, uint64_t n_queries, uint32_t* out,
+                                        int32_t n_threads)
+{
+    if (!wavelet_ok(tree) || n_queries > 0xFFFFFFFFull || (n_queries && (!positions || !symbols || !out))) return hipErrorInvalidValue;
+    const int threads = host_threads(n_threads);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 k = 0; k < int64(n_queries); ++k) out[k] = wt_rank_host(*tree, positions[k], symbols[k]);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_wavelet_rank_range_host(const nvbio_hip_wavelet_tree* tree, const uint32_t* ranges, const uint8_t* symbols, uint64_t n_queries, uint32_t* out,
+                                              int32_t n_threads)
+{
+    if (!wavelet_ok(tree) || n_queries > 0xFFFFFFFFull || (n_queries && (!ranges || !symbols || !out))) return hipErrorInvalidValue;
+    const int threads = host_threads(n_threads);
+    #pragma omp parallel for schedule(static) num_threads(threads)
+    for (int64 k = 0; k < int64(n_queries); ++k)
+    {
+        out[2 * k]     = wt_rank_host(*tree, ranges[2 * k], symbols[k]);
+        out[2 * k + 1] = wt_rank_host(*tree, ranges[2 * k + 1], symbols[k]);
+    }
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_wavelet_fm_L2_host(const nvbio_hip_wavelet_tree* tree, uint32_t* L2_out, int32_t n_threads)
+{
+    (void)n_threads;
+    if (!wavelet_ok(tree) || !L2_out) return hipErrorInvalidValue;
+    const uint32 K = 1u << tree->symbol_size;
+    L2_out[0] = 0u;
+    for (uint32 c = 0; c < K; ++c) L2_out[c + 1u] = L2_out[c] + wt_rank_host(*tree, tree->size - 1u, c);
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_wavelet_fm_match_host(const nvbio_hip_wavelet_fmindex* fmi, const nvbio_hip_byte_string_set* patterns, uint64_t n, uint32_t* ranges_out,
+                                            int32_t n_threads)
+{
+    if (!wavelet_fm_ok(fmi) || !patterns || n > 0xFFFFFFFFull || (n && (!patterns->begin || !ranges_out))) return hipErrorInvalidValue;
+    if (n && !patterns->symbols && patterns->n_symbols) return hipErrorInvalidValue;
+    const int threads = host_threads(n_threads);
+    const uint32 K = 1u << fmi->bwt.symbol_size;
+    const uint64 n_symbols = patterns->symbols ? patterns->n_symbols : 0u;
+    #pragma omp parallel for schedule(dynamic, 256) num_threads(threads)
+    for (int64 id = 0; id < int64(n); ++id)
+    {
+        const uint64 beg = patterns->begin[id];
+        uint64 len = patterns->length ? patterns->length[id] : patterns->fixed_length;
+        if (beg >= n_symbols) len = 0u; else if (len > n_symbols - beg) len = n_symbols - beg;
+        uint32 x = 0u, y = fmi->length;
+        for (uint64 i = len; i-- > 0u && x <= y;)
+        {
+            const uint32 c = patterns->symbols[beg + i];
+            if (c >= K) { x = 1u; y = 0u; break; }
+            const uint32 rx = wt_fm_rank_host(*fmi, x - 1u, c), ry = wt_fm_rank_host(*fmi, y, c);
+            x = fmi->L2[c] + rx + 1u;
+            y = fmi->L2[c] + ry;
+        }
+        ranges_out[2 * id] = x; ranges_out[2 * id + 1] = y;
+    }
+    return hipSuccess;
+}
+
+NVB_API int nvbio_hip_wavelet_fm_locate_host(const nvbio_hip_wavelet_fmindex* fmi, const uint32_t* rows, uint64_t n_rows, uint32_t* positions_out, int32_t n_threads)
+{
+    if (!wavelet_fm_ok(fmi) || !fmi->ssa || fmi->sa_int == 0u) return hipErrorInvalidValue;
+    if (n_rows > 0xFFFFFFFFull || (n_rows && (!rows || !positions_out))) return hipErrorInvalidValue;
+    const int threads = host_threads(n_threads);
+    #pragma omp parallel for schedule(dynamic, 256) num_threads(threads)
+    for (int64 id = 0; id < int64(n_rows); ++id)
+    {
+        uint32 j = rows[id], t = 0u;
+        while (j <= fmi->length && j % fmi->sa_int != 0u && t <= fmi->length)
+        {
+            if (j != fmi->primary)
+            {
+                const uint32 c = wt_text_host(fmi->bwt, j < fmi->primary ? j : j - 1u);
+                j = fmi->L2[c] + wt_fm_rank_host(*fmi, j, c);                  // fmindex_inl.h:491-492
+            }
+            else j = 0u;
+            ++t;
+        }
+        positions_out[id] = (j <= fmi->length && j % fmi->sa_int == 0u) ? fmi->ssa[j / fmi->sa_int] + t : 0xFFFFFFFFu;
+    }
     return hipSuccess;
 }

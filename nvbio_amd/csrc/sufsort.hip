@@ -1,5 +1,6 @@
 // sufsort.hip -- suffix sorting and BWT construction of one 2-bit packed text on the device: the plain-string front door of the
-// reference's nvbio/sufsort (cuda::suffix_sort, cuda::bwt, cuda::find_primary).  DESIGN.md 3.13.
+// reference's nvbio/sufsort (cuda::suffix_sort, cuda::bwt, cuda::find_primary).  DESIGN.md 3.13.  A byte text of 1 to 8 bits a symbol
+// goes through the same rounds from a round-0 key of its own (the `_bytes` entries).
 //
 // Output convention (compat/nvbio/fmindex/bwt.h): SA has n + 1 rows, SA[0] = n is the empty suffix, and a suffix that is a proper
 // prefix of another sorts first ($ < A).  Below, "row" k in [0, n) is SA row k + 1: only the n real suffixes are sorted.
@@ -218,8 +219,10 @@ static ss_buffers ss_carve(void* temp, uint64_t n)
 // The sorting rounds over the n round-0 keys in keysA with ids 0..n-1 in idsA: sa_rows[row] = the suffix on that row, rank[i] = its
 // row + 1.  SET_KEY0: the keys are a string set's (sufsort_set_key0_kernel) and round 0 takes that head rule; d_total, if not NULL, is
 // the device word that must equal n: round 0 writes nothing but scratch unless it does, and its wait brings the word to the host too.
+// h0: the symbols a round-0 key orders by, the first doubling step (29 for the 2-bit keys, floor(58 / S) for a byte text's).
 template <bool SET_KEY0>
-static int ss_rounds(const ss_buffers& bufs, uint64_t n, uint32_t* sa_rows, void* prim, size_t prim_bytes, hipStream_t s, const uint64_t* d_total = nullptr)
+static int ss_rounds(const ss_buffers& bufs, uint64_t n, uint32_t* sa_rows, void* prim, size_t prim_bytes, hipStream_t s, const uint64_t* d_total = nullptr,
+                     const uint64_t h0 = SS_K0)
 {
     uint32_t* const rowsA = bufs.rowsA, * const rowsB = bufs.rowsB, * const rank = bufs.rank;
     const uint32_t b = 64u - uint32_t(__builtin_clzll(n));         // a rank is at most n
@@ -230,18 +233,18 @@ static int ss_rounds(const ss_buffers& bufs, uint64_t n, uint32_t* sa_rows, void
     rocprim::double_buffer<uint32_t> ids(bufs.idsA, bufs.idsB);
     uint32_t* urow = nullptr;                                       // round 0: position k is row k
     uint32_t* urow_next = rowsA;
-    uint64_t m = n, h = SS_K0;
+    uint64_t m = n, h = h0;
     uint32_t end_bit = 64u;
     while (true)
     {
         if (hipError_t e = rocprim::radix_sort_pairs(prim, prim_bytes, keys, ids, size_t(m), 0u, end_bit, s)) return e;
         uint32_t* head = reinterpret_cast<uint32_t*>(keys.alternate());
         uint32_t* keep = head + m;
-        if (SET_KEY0 && h == SS_K0) hipLaunchKernelGGL(sufsort_heads_kernel<true>, dim3(ss_blocks(m)), block, 0, s, keys.current(), m, head);
+        if (SET_KEY0 && h == h0) hipLaunchKernelGGL(sufsort_heads_kernel<true>, dim3(ss_blocks(m)), block, 0, s, keys.current(), m, head);
         else hipLaunchKernelGGL(sufsort_heads_kernel<false>, dim3(ss_blocks(m)), block, 0, s, keys.current(), m, head);
         if (hipError_t e = hipGetLastError()) return e;
         if (hipError_t e = rocprim::inclusive_scan(prim, prim_bytes, head, head, size_t(m), rocprim::maximum<uint32_t>(), s)) return e;
-        const bool check_total = SET_KEY0 && h == SS_K0 && d_total;
+        const bool check_total = SET_KEY0 && h == h0 && d_total;
         if (check_total) hipLaunchKernelGGL(sufsort_update_kernel<true>, dim3(ss_blocks(m)), block, 0, s, ids.current(), head, urow, m, rank, sa_rows, keep, d_total);
         else hipLaunchKernelGGL(sufsort_update_kernel<false>, dim3(ss_blocks(m)), block, 0, s, ids.current(), head, urow, m, rank, sa_rows, keep, (const uint64_t*)nullptr);
         if (hipError_t e = hipGetLastError()) return e;
@@ -287,6 +290,76 @@ static int ss_check(const uint32_t* words, uint32_t bits, uint64_t n)
     if (bits != 2u) return hipErrorInvalidValue;
     if (n == 0u || n > SS_MAX_N) return hipErrorInvalidValue;
     return hipSuccess;
+}
+
+// ---- a byte text: one symbol per byte, S = symbol_size bits of it (nvbio_hip_suffix_sort_bytes / nvbio_hip_bwt_bytes) ----
+//
+// The round-0 key of suffix i: its first K0 = floor(58 / S) symbols, most significant first (symbol j at bits [64 - S (j + 1), 64 - S j)),
+// symbols past the end as 0, then min(n - i, K0) in the low 6 bits (K0 <= 58 fits, and S K0 <= 58 leaves them free).  The claim above
+// sufsort_key0_kernel uses of the alphabet only that the pad, 0, is its smallest symbol: read 29 as K0 and A as symbol 0 and it holds as
+// it stands, so the rounds take these keys with h0 = K0.
+__global__ __launch_bounds__(256) void sufsort_bytes_key0_kernel(const uint8_t* __restrict__ symbols, const uint32_t S, const uint32_t k0, const uint64_t n,
+                                                                 uint64_t* __restrict__ keys, uint32_t* __restrict__ ids)
+{
+    const uint64_t i = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t rem = n - i;
+    const uint32_t len = rem < k0 ? uint32_t(rem) : k0, mask = (1u << S) - 1u;
+    uint64_t v = 0u;
+    uint32_t sh = 64u;
+    for (uint32_t j = 0; j < len; ++j)
+    {
+        sh -= S;
+        v |= uint64_t(symbols[i + j] & mask) << sh;
+    }
+    keys[i] = v | len;
+    ids[i]  = uint32_t(i);
+}
+
+// bwt[j] = T[SA[row] - 1] over the rows but the primary (rank[0]), one byte a symbol.  A lane owns four rows -- one 32-bit word of the
+// output -- and issues its four SA loads, then its four symbol loads, before it uses the first.
+__global__ __launch_bounds__(256) void sufsort_bytes_bwt_kernel(const uint8_t* __restrict__ symbols, const uint32_t mask, const uint64_t n, const uint32_t* __restrict__ sa,
+                                                                const uint32_t* __restrict__ rank, uint8_t* __restrict__ bwt_out, const uint32_t word_stores)
+{
+    const uint64_t w = uint64_t(blockIdx.x) * 256u + threadIdx.x;
+    const uint64_t j0 = w * 4u;
+    if (j0 >= n) return;
+    const uint64_t primary = rank[0];
+    uint32_t s[4], sym[4];
+    #pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q)
+    {
+        const uint64_t j = j0 + q;
+        s[q] = j < n ? sa[j + (j >= primary ? 1u : 0u)] : 0u;
+    }
+    #pragma unroll
+    for (uint32_t q = 0; q < 4u; ++q) sym[q] = s[q] ? uint32_t(symbols[s[q] - 1u]) & mask : 0u;        // s is never 0 off the primary row
+    if (word_stores && j0 + 4u <= n) reinterpret_cast<uint32_t*>(bwt_out)[w] = sym[0] | (sym[1] << 8) | (sym[2] << 16) | (sym[3] << 24);
+    else
+    {
+        #pragma unroll
+        for (uint32_t q = 0; q < 4u; ++q) if (j0 + q < n) bwt_out[j0 + q] = uint8_t(sym[q]);
+    }
+}
+
+static int ss_bytes_check(const uint8_t* symbols, uint32_t symbol_size, uint64_t n)
+{
+    if (!symbols) return hipErrorInvalidValue;
+    if (symbol_size < 1u || symbol_size > 8u) return hipErrorInvalidValue;
+    if (n == 0u || n > SS_MAX_N) return hipErrorInvalidValue;
+    return hipSuccess;
+}
+
+static int ss_bytes_sort(const uint8_t* symbols, uint32_t S, uint64_t n, uint32_t* sa_out, uint32_t** rank_out, void* temp, uint64_t temp_bytes, hipStream_t s)
+{
+    const ss_buffers bufs = ss_carve(temp, n);
+    *rank_out = bufs.rank;
+    const uint32_t k0 = 58u / S;
+    if (hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sa_out), int(uint32_t(n)), 1u, s)) return e;      // SA[0] = n
+    g_last_kernel = "sufsort_bytes_key0_kernel";
+    hipLaunchKernelGGL(sufsort_bytes_key0_kernel, dim3(ss_blocks(n)), dim3(256), 0, s, symbols, S, k0, n, bufs.keysA, bufs.idsA);
+    if (hipError_t e = hipGetLastError()) return e;
+    return ss_rounds<false>(bufs, n, sa_out + 1, bufs.end, size_t(temp_bytes - uint64_t(bufs.end - reinterpret_cast<uint8_t*>(temp))), s, nullptr, k0);
 }
 
 // ---- the suffixes of a string set (cuda::suffix_sort(string_set, ..), cuda::bwt(ConcatenatedStringSet, ..)) ----
@@ -541,6 +614,44 @@ NVB_API int nvbio_hip_bwt(const uint32_t* words, uint32_t bits, uint32_t big_end
     const uint64_t n_out_words = 4u * ((n + 63u) / 64u);
     g_last_kernel = "sufsort_bwt_kernel";
     hipLaunchKernelGGL(sufsort_bwt_kernel, dim3(ss_blocks(n_out_words)), dim3(256), 0, s, words, be, n, sa, rank, n_out_words, bwt_words_out);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (ssa_out)
+    {
+        const uint64_t n_ssa = (n + sa_int) / sa_int;               // ceil((n + 1) / sa_int)
+        hipLaunchKernelGGL(sufsort_ssa_kernel, dim3(ss_blocks(n_ssa)), dim3(256), 0, s, sa, n_ssa, sa_int, ssa_out);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (hipError_t e = hipMemcpyAsync(primary_out, rank, 4u, hipMemcpyDeviceToHost, s)) return e;       // rank[0]: the row of suffix 0
+    return hipStreamSynchronize(s);
+}
+
+NVB_API uint64_t nvbio_hip_suffix_sort_bytes_temp_bytes(uint64_t n) { return nvbio_hip_suffix_sort_temp_bytes(n); }
+
+NVB_API int nvbio_hip_suffix_sort_bytes(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t* sa_out, void* temp, uint64_t temp_bytes, void* stream)
+{
+    if (int e = ss_bytes_check(symbols, symbol_size, n)) return e;
+    if (!sa_out || !temp || temp_bytes < nvbio_hip_suffix_sort_bytes_temp_bytes(n)) return hipErrorInvalidValue;
+    uint32_t* rank = nullptr;
+    return ss_bytes_sort(symbols, symbol_size, n, sa_out, &rank, temp, temp_bytes, to_stream(stream));
+}
+
+NVB_API uint64_t nvbio_hip_bwt_bytes_temp_bytes(uint64_t n) { return nvbio_hip_bwt_temp_bytes(n); }
+
+NVB_API int nvbio_hip_bwt_bytes(const uint8_t* symbols, uint32_t symbol_size, uint64_t n, uint32_t sa_int, uint8_t* bwt_out, uint32_t* primary_out,
+                                uint32_t* ssa_out, uint32_t* sa_out, void* temp, uint64_t temp_bytes, void* stream)
+{
+    if (int e = ss_bytes_check(symbols, symbol_size, n)) return e;
+    if (!bwt_out || !primary_out || (ssa_out && sa_int == 0u)) return hipErrorInvalidValue;
+    if (!temp || temp_bytes < nvbio_hip_bwt_bytes_temp_bytes(n)) return hipErrorInvalidValue;
+    hipStream_t s = to_stream(stream);
+    uint8_t* p = reinterpret_cast<uint8_t*>(temp);
+    uint32_t* sa = sa_out ? sa_out : reinterpret_cast<uint32_t*>(p);
+    p += ss_align((n + 1u) * 4u);
+    uint32_t* rank = nullptr;
+    if (int e = ss_bytes_sort(symbols, symbol_size, n, sa, &rank, p, temp_bytes - ss_align((n + 1u) * 4u), s)) return e;
+    g_last_kernel = "sufsort_bytes_bwt_kernel";
+    const uint32_t word_stores = (reinterpret_cast<uintptr_t>(bwt_out) & 3u) == 0u ? 1u : 0u;
+    hipLaunchKernelGGL(sufsort_bytes_bwt_kernel, dim3(ss_blocks((n + 3u) / 4u)), dim3(256), 0, s, symbols, (1u << symbol_size) - 1u, n, sa, rank, bwt_out, word_stores);
     if (hipError_t e = hipGetLastError()) return e;
     if (ssa_out)
     {

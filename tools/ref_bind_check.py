@@ -578,6 +578,18 @@ void instantiate(QGramIndexDevice& d, QGramIndexHost& h, QGramSetIndexDevice& s,
 """, main="int main() { return 0; }\n"))
 
 
+# the reference's wavelet tree programs: its own example (BWT of a protein string through cuda::bwt on an 8-bit PackedVector, the tree of the
+# BWT, L2 by host-side ranks, fm_index<WaveletTree, ..>::match of every suffix) and its own test (setup of 100 k random bytes, text() through
+# nvbio::transform on the device, seven known ranks).  Both stop here at the first device allocation and run on the GPU box from oracle/_ref/.
+WHOLE.append(dict(name="examples/waveletfm/waveletfm.cu, whole TU, compiled as it lies and linked: PackedVector<.., 8, true>, from_string / to_string<PROTEIN>, cuda::bwt on an 8-bit string, "
+                       "WaveletTreeStorage<device_tag> / setup / plain_view / rank, fm_index<wavelet view, null_type, L2 iterator> / match",
+                  tu="examples/waveletfm/waveletfm.cu", install="ref_waveletfm", main=None, run=[], expect="text: ACDEFGHIKLMNOPQRSTVWYBZX", may_abort=True))
+WHOLE.append(dict(name="nvbio-test/wavelet_test.cu, whole TU, compiled as it lies and linked with a three-line main: setup of a device tree from a device byte vector, text() as the functor "
+                       "of nvbio::transform<device_tag>, the seven known ranks",
+                  tu="nvbio-test/wavelet_test.cu", install="ref_wavelet_test", main="namespace nvbio { int wavelet_test(int argc, char* argv[]); }\nint main(int argc, char** argv) { return nvbio::wavelet_test(argc - 1, argv + 1); }\n",
+                  run=[], expect="wavelet test... started", may_abort=True))
+
+
 def sw_benchmark_files(tmp):
     """a 3 000-bp FASTA reference and 64 FASTQ reads cut from it, for the host part of the sw-benchmark run"""
     import random
